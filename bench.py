@@ -3,7 +3,13 @@
 MI355X-native engine, per BASELINE.json.
 
 Contract: `python bench.py --gpus N --steps K --warmup W`; for N>1 launched
-by torchrun with one rank per GPU; rank 0 prints ONE JSON line.  A "step" is
+by torchrun with one rank per GPU; rank 0 prints ONE JSON line.  A plain run
+does only what the headline figure needs: set up, prefill the prompt, warm
+up, time K decode steps, print.  `--full` adds every other leg (per-kernel
+roofline stats, prefill rate, CPU baseline, the model matrix); without it
+those keys of the JSON line are null.  `--dump-outputs DIR` writes what the
+timed decode call returned (the K greedy token ids) as DIR/tokens.npy.
+A "step" is
 one greedy KV-cached decode token (the reference's per-token hot loop,
 text_model.rs:397-495; rate convention excludes the first token like
 master.rs:131-166).  N>1 = the model layer-sharded as contiguous pipeline
@@ -12,8 +18,8 @@ default.rs:11-130) — total work fixed, so "scaling": "strong".
 
 Synthetic data: seeded-uniform token ids (seed 299792458 = cake's default,
 lib.rs:180); random-init weights of the named architecture (no network).
-The oracle (CPU restatement) is timed beside it as cpu_baseline — baseline
-only, never the target.
+With `--full` the oracle (CPU restatement) is timed beside it as
+cpu_baseline — baseline only, never the target.
 """
 import argparse
 import json
@@ -247,15 +253,28 @@ def main():
     ap.add_argument("--steps", type=int, default=256)
     ap.add_argument("--warmup", type=int, default=16)
     ap.add_argument("--model", default="llama3-8b")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline decode "
+                         "rate: roofline stats (--stats-steps), prefill "
+                         "rate (--prefill-len), CPU baseline, --matrix")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the token ids the "
+                         "timed decode call returned to DIR/tokens.npy "
+                         "(float64, one per step)")
     ap.add_argument("--prompt-len", type=int, default=128)
     ap.add_argument("--prefill-len", type=int, default=2048,
-                    help="tokens for the prefill-rate measurement (0=skip)")
+                    help="with --full: tokens for the prefill-rate "
+                         "measurement (0=skip)")
     ap.add_argument("--max-seq", type=int, default=4096)
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--stats-steps", type=int, default=8)
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--stats-steps", type=int, default=8,
+                    help="with --full: eager decode steps timed per kernel "
+                         "for the roofline (0=skip)")
     ap.add_argument("--matrix", default="llama3-70b,qwen3-32b-fp8,qwen3-0.6b",
-                    help="comma-separated extra BASELINE configs benched "
+                    help="with --full: comma-separated extra BASELINE "
+                         "configs benched "
                          "compactly at N=1 into the 'matrix' key of the one "
                          "JSON line ('' = none)")
     ap.add_argument("--matrix-steps", type=int, default=24)
@@ -356,9 +375,18 @@ def main():
     log(rank, f"[bench] decode: {args.steps} steps in {elapsed:.3f}s = "
         f"{decode_tok_s:.1f} tok/s")
 
+    # ---- what the timed call returned, for build-to-build comparison ------
+    if rank == 0 and args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "tokens.npy"),
+                np.asarray(toks, dtype=np.float64))
+        log(rank, f"[bench] wrote {len(toks)} token ids to "
+            f"{os.path.join(args.dump_outputs, 'tokens.npy')}")
+
+    # ---- everything below is a --full leg --------------------------------
     # ---- roofline stats segment (eager, hipEvent-timed) ------------------
     roofline = None
-    if args.stats_steps > 0:
+    if args.full and args.stats_steps > 0:
         eng.set_stats(True)
         if rank == 0:
             eng.decode(args.stats_steps)
@@ -373,7 +401,7 @@ def main():
 
     # ---- prefill rate ----------------------------------------------------
     prefill_tok_s = None
-    if args.prefill_len > 0 and args.prefill_len <= args.max_seq:
+    if args.full and 0 < args.prefill_len <= args.max_seq:
         pf = rng.integers(0, cfg_json["vocab_size"],
                           size=args.prefill_len).astype(np.uint32)
         # two untimed warm passes: the first builds the per-shape GEMM
@@ -407,7 +435,7 @@ def main():
 
     # ---- CPU baseline (rank 0, N=1 only) ---------------------------------
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         log(rank, "[bench] timing CPU baseline (oracle, bounded sample) ...")
         cpu = cpu_baseline(cfg_json, prompt_len=args.prompt_len)
         log(rank, f"[bench] cpu_baseline: {cpu['value']:.3f} tok/s on "
@@ -415,7 +443,7 @@ def main():
 
     # ---- matrix mode: the other BASELINE configs, compactly (N=1 only) ---
     matrix = None
-    if rank == 0 and world == 1 and args.matrix:
+    if args.full and rank == 0 and world == 1 and args.matrix:
         matrix = {}
         for m in [s for s in args.matrix.split(",") if s]:
             if m == args.model:
@@ -459,7 +487,7 @@ def main():
                 "parallelism": f"pp{n_gpus}",
             },
             "prefill_tok_s": round(prefill_tok_s, 1) if prefill_tok_s else None,
-            "prefill_len": args.prefill_len,
+            "prefill_len": args.prefill_len if args.full else None,
             "prefill_roofline": build_prefill_roofline(cfg_json,
                                                        prefill_tok_s),
             "roofline": roofline,
