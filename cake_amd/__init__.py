@@ -60,6 +60,12 @@ def _load_lib():
     lib.cake_hip_op_linear.argtypes = [c, c, c, fp, fp, fp, c]
     lib.cake_hip_op_silu_mul.argtypes = [ctypes.c_long, fp, fp, fp, c]
     lib.cake_hip_op_rope.argtypes = [c, c, c, c, fp, fp, fp, fp, c]
+    f = ctypes.c_float
+    lib.cake_hip_op_kv_store.argtypes = [c, c, c, c, c, c, c, fp, fp, fp, fp,
+                                         fp, f, fp, fp, fp, fp, c]
+    lib.cake_hip_op_attn_prefill.argtypes = [c] * 11 + [fp] * 5 + [c]
+    lib.cake_hip_op_attn_decode.argtypes = [c] * 8 + [fp] * 4 + [c]
+    lib.cake_hip_attn_dispatch.argtypes = [c, c, c, c, ctypes.POINTER(c)]
     lib.cake_hip_kernel_stats.argtypes = [p, ctypes.c_char_p, c]
     lib.cake_hip_stats_reset.argtypes = [p]
     lib.cake_hip_set_stats.argtypes = [p, c]
@@ -151,6 +157,94 @@ def op_rope(x, cos, sin, device=0):
         b, h, s, d, xp, cp, sp,
         out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), device))
     return out
+
+
+def _f32_shaped(a, shape, name):
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if a.shape != tuple(shape):
+        raise ValueError(f"{name}: shape {a.shape}, expected {tuple(shape)}")
+    return a, a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+
+
+def op_kv_store(qkv, cos, sin, kc, vc, vtc, pos0, nh, nkv, q_norm=None,
+                k_norm=None, eps=1e-6, decode=False, device=0):
+    """Rope [+ QK-norm] + KV-cache store of raw qkv rows (S, (nh+2*nkv)*hd)
+    at positions pos0.. (decode=True: the one-row decode kernel).  kc/vc
+    (nkv, max_seq, hd) and vtc (nkv, hd, max_seq) are the PRIOR cache images;
+    returns (roped q (S, nh, hd), kc, vc, vtc) after the store."""
+    kc = np.array(kc, dtype=np.float32, order="C")
+    nkv_, max_seq, hd = kc.shape if kc.ndim == 3 else (0, 0, 0)
+    qkv = np.ascontiguousarray(qkv, dtype=np.float32)
+    S = qkv.shape[0]
+    _, qp = _f32_shaped(qkv, (S, (nh + 2 * nkv) * hd), "qkv")
+    kc, kp = _f32_shaped(kc, (nkv, max_seq, hd), "kc")
+    vc, vp = _f32_shaped(np.array(vc, dtype=np.float32, order="C"),
+                         (nkv, max_seq, hd), "vc")
+    vtc, vtp = _f32_shaped(np.array(vtc, dtype=np.float32, order="C"),
+                           (nkv, hd, max_seq), "vtc")
+    _c, cp = _f32_shaped(cos, (max_seq, hd // 2), "cos")
+    _s, sp = _f32_shaped(sin, (max_seq, hd // 2), "sin")
+    qn = kn = qnp = knp = None
+    if q_norm is not None:
+        qn, qnp = _f32_shaped(q_norm, (hd,), "q_norm")
+    if k_norm is not None:
+        kn, knp = _f32_shaped(k_norm, (hd,), "k_norm")
+    q_out = np.empty((S, nh, hd), dtype=np.float32)
+    _check(_lib.cake_hip_op_kv_store(
+        S, pos0, 1 if decode else 0, nh, nkv, hd, max_seq, qp, cp, sp, qnp,
+        knp, ctypes.c_float(eps), kp, vp, vtp,
+        q_out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), device))
+    return q_out, kc, vc, vtc
+
+
+def op_attn_prefill(q, kc, vc, vtc, pos0, window=0, variant=None, device=0):
+    """Prefill attention of post-rope q (S, nh, hd) at positions pos0.. over
+    cache images kc/vc (nkv, max_seq, hd), vtc (nkv, hd, max_seq).  variant =
+    (pfv, nw, split, deep); default: plain v2 NW=8 at hd 128, else the
+    generic kernel.  Returns (S, nh*hd)."""
+    q = np.ascontiguousarray(q, dtype=np.float32)
+    S, nh, hd = q.shape
+    kc = np.ascontiguousarray(kc, dtype=np.float32)
+    nkv, max_seq = kc.shape[0], kc.shape[1]
+    if variant is None:
+        variant = (2, 8, 0, 0) if hd == 128 else (0, 0, 0, 0)
+    pfv, nw, split, deep = variant
+    _, qp = _f32_shaped(q, (S, nh, hd), "q")
+    _, kp = _f32_shaped(kc, (nkv, max_seq, hd), "kc")
+    _v, vp = _f32_shaped(vc, (nkv, max_seq, hd), "vc")
+    _t, vtp = _f32_shaped(vtc, (nkv, hd, max_seq), "vtc")
+    out = np.empty((S, nh * hd), dtype=np.float32)
+    _check(_lib.cake_hip_op_attn_prefill(
+        S, pos0, nh, nkv, hd, max_seq, window, pfv, nw, split, deep, qp, kp,
+        vp, vtp, out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), device))
+    return out
+
+
+def op_attn_decode(q, kc, vc, pos, window=0, nchunk=8, repeats=1, device=0):
+    """Decode attention of q (nh, hd) at position pos over kc/vc (nkv,
+    max_seq, hd); the kernel runs `repeats` times back to back on arrival
+    counters zeroed once.  Returns (repeats, nh*hd)."""
+    q = np.ascontiguousarray(q, dtype=np.float32)
+    nh, hd = q.shape
+    kc = np.ascontiguousarray(kc, dtype=np.float32)
+    nkv, max_seq = kc.shape[0], kc.shape[1]
+    _, qp = _f32_shaped(q, (nh, hd), "q")
+    _, kp = _f32_shaped(kc, (nkv, max_seq, hd), "kc")
+    _v, vp = _f32_shaped(vc, (nkv, max_seq, hd), "vc")
+    out = np.empty((max(repeats, 0), nh * hd), dtype=np.float32)
+    _check(_lib.cake_hip_op_attn_decode(
+        nh, nkv, hd, max_seq, pos, window, nchunk, repeats, qp, kp, vp,
+        out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), device))
+    return out
+
+
+def attn_dispatch(S, nh, nkv, hd):
+    """The product's launch choices for this shape (host only): dict with the
+    prefill variant and the grouped-decode grid_y (0 = per-head kernel)."""
+    o = (ctypes.c_int * 6)()
+    _check(_lib.cake_hip_attn_dispatch(S, nh, nkv, hd, o))
+    return dict(pfv=o[0], nw=o[1], split=o[2], deep=o[3], split_min_s=o[4],
+                decode_grid_y=o[5])
 
 
 def comm_id() -> bytes:

@@ -1800,6 +1800,222 @@ extern "C" int cake_hip_op_rope(int b, int h, int s, int d, const float* x,
   return down16(o.a, o.fc, out, n, o.s);
 }
 
+// ---- attention + KV-store op entries ---------------------------------------
+// Per-call buffers with exactly the engine's sizes (freed on every return
+// path), the real launch wrappers on a private stream.  Arguments are
+// validated before any HIP call so the error paths run without a GPU.
+struct OpBufs {
+  std::vector<void*> ptrs;
+  hipStream_t s = nullptr;
+  ~OpBufs() {
+    for (void* p : ptrs) hipFree(p);
+    if (s) hipStreamDestroy(s);
+  }
+};
+static int ob_alloc(OpBufs& b, void** p, size_t bytes) {
+  int r = dev_alloc(p, bytes);
+  if (r) return r;
+  b.ptrs.push_back(*p);
+  return 0;
+}
+// host f32 -> fresh device bf16 buffer of n elements
+static int ob_up16(OpBufs& b, const float* src, size_t n, u16** dst) {
+  void *stage = nullptr, *d = nullptr;
+  int r;
+  if ((r = ob_alloc(b, &stage, n * 4))) return r;
+  if ((r = ob_alloc(b, &d, n * 2))) return r;
+  *dst = (u16*)d;
+  return up16(src, (float*)stage, *dst, n, b.s);
+}
+static int ob_down16(OpBufs& b, const u16* src, size_t n, float* dst) {
+  void* stage = nullptr;
+  int r;
+  if ((r = ob_alloc(b, &stage, n * 4))) return r;
+  return down16(src, (float*)stage, dst, n, b.s);
+}
+static int ob_upf32(OpBufs& b, const void* src, size_t bytes, void** dst) {
+  int r;
+  if ((r = ob_alloc(b, dst, bytes))) return r;
+  HIP_TRY(hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, b.s));
+  return 0;
+}
+static int attn_geom_err(const char* who, int nh, int nkv, int hd,
+                         int max_seq) {
+  if (nh <= 0 || nkv <= 0 || nh % nkv != 0)
+    return set_err(5, "%s: nh %d must be a positive multiple of nkv %d", who,
+                   nh, nkv);
+  if (hd < 8 || hd > 128 || hd % 8 != 0)
+    return set_err(5, "%s: hd %d must be a multiple of 8 in [8,128]", who,
+                   hd);
+  if (max_seq < 32 || max_seq % 32 != 0)
+    return set_err(5, "%s: max_seq %d must be a positive multiple of 32",
+                   who, max_seq);
+  return 0;
+}
+
+extern "C" int cake_hip_op_kv_store(int S, int pos0, int decode, int nh,
+                                    int nkv, int hd, int max_seq,
+                                    const float* qkv, const float* cosv,
+                                    const float* sinv, const float* q_norm,
+                                    const float* k_norm, float eps, float* kc,
+                                    float* vc, float* vtc, float* q_out,
+                                    int device) {
+  const char* who = "op_kv_store";
+  int r = attn_geom_err(who, nh, nkv, hd, max_seq);
+  if (r) return r;
+  if (S < 1 || pos0 < 0 || pos0 + S > max_seq)
+    return set_err(5, "%s: rows [%d,%d+%d) outside the cache (max_seq %d)",
+                   who, pos0, pos0, S, max_seq);
+  if (decode && S != 1)
+    return set_err(5, "%s: the decode store takes one row (got %d)", who, S);
+  if ((q_norm == nullptr) != (k_norm == nullptr))
+    return set_err(5, "%s: q_norm and k_norm go together", who);
+  OpBufs b;
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreate(&b.s));
+  const int Nq = (nh + 2 * nkv) * hd;
+  const size_t ncache = (size_t)nkv * max_seq * hd;
+  const size_t ntab = (size_t)max_seq * (hd / 2);
+  u16 *dqkv, *dkc, *dvc, *dvtc, *dqn = nullptr, *dkn = nullptr;
+  void *dcos, *dsin, *dpos;
+  if ((r = ob_up16(b, qkv, (size_t)S * Nq, &dqkv))) return r;
+  if ((r = ob_up16(b, kc, ncache, &dkc))) return r;
+  if ((r = ob_up16(b, vc, ncache, &dvc))) return r;
+  if ((r = ob_up16(b, vtc, ncache, &dvtc))) return r;
+  if (q_norm) {
+    if ((r = ob_up16(b, q_norm, hd, &dqn))) return r;
+    if ((r = ob_up16(b, k_norm, hd, &dkn))) return r;
+  }
+  if ((r = ob_upf32(b, cosv, ntab * 4, &dcos))) return r;
+  if ((r = ob_upf32(b, sinv, ntab * 4, &dsin))) return r;
+  if ((r = ob_upf32(b, &pos0, sizeof(int), &dpos))) return r;
+  if (decode)
+    launch_rope_store_decode(dqkv, dkc, dvc, dvtc, (const float*)dcos,
+                             (const float*)dsin, (const int*)dpos, nh, nkv,
+                             hd, hd, max_seq, dqn, dkn, eps, b.s);
+  else
+    launch_rope_store_prefill(dqkv, dkc, dvc, dvtc, (const float*)dcos,
+                              (const float*)dsin, pos0, S, nh, nkv, hd, hd,
+                              max_seq, Nq, dqn, dkn, eps, b.s);
+  HIP_TRY(hipGetLastError());
+  std::vector<float> rows((size_t)S * Nq);
+  if ((r = ob_down16(b, dqkv, rows.size(), rows.data()))) return r;
+  for (int i = 0; i < S; ++i)
+    memcpy(q_out + (size_t)i * nh * hd, rows.data() + (size_t)i * Nq,
+           sizeof(float) * nh * hd);
+  if ((r = ob_down16(b, dkc, ncache, kc))) return r;
+  if ((r = ob_down16(b, dvc, ncache, vc))) return r;
+  return ob_down16(b, dvtc, ncache, vtc);
+}
+
+extern "C" int cake_hip_op_attn_prefill(int S, int pos0, int nh, int nkv,
+                                        int hd, int max_seq, int window,
+                                        int pfv, int nw, int split, int deep,
+                                        const float* q, const float* kc,
+                                        const float* vc, const float* vtc,
+                                        float* out, int device) {
+  const char* who = "op_attn_prefill";
+  int r = attn_geom_err(who, nh, nkv, hd, max_seq);
+  if (r) return r;
+  if (S < 1 || pos0 < 0 || pos0 + S > max_seq)
+    return set_err(5, "%s: rows [%d,%d+%d) outside the cache (max_seq %d)",
+                   who, pos0, pos0, S, max_seq);
+  if (window < 0) return set_err(5, "%s: window %d < 0", who, window);
+  // what the dispatcher can express: hd 128 -> v1, or v2 with 4|8 waves and
+  // at most one of split / deep; any other hd -> the generic kernel only
+  const bool ok =
+      hd == 128 ? ((pfv == 1 && nw == 8 && !split && !deep) ||
+                   (pfv == 2 && (nw == 4 || nw == 8) &&
+                    (split == 0 || split == 1) && deep >= 0 && deep <= 2 &&
+                    !(split && deep)))
+                : (pfv == 0 && nw == 0 && !split && !deep);
+  if (!ok)
+    return set_err(5, "%s: variant {pfv %d, nw %d, split %d, deep %d} is "
+                   "not dispatchable at hd %d", who, pfv, nw, split, deep,
+                   hd);
+  OpBufs b;
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreate(&b.s));
+  const int Sq = nh * hd;
+  const size_t ncache = (size_t)nkv * max_seq * hd;
+  u16 *dq, *dkc, *dvc, *dvtc;
+  void *dout, *dws;
+  if ((r = ob_up16(b, q, (size_t)S * Sq, &dq))) return r;
+  if ((r = ob_up16(b, kc, ncache, &dkc))) return r;
+  if ((r = ob_up16(b, vc, ncache, &dvc))) return r;
+  if ((r = ob_up16(b, vtc, ncache, &dvtc))) return r;
+  if ((r = ob_alloc(b, &dout, (size_t)S * Sq * 2))) return r;
+  if ((r = ob_alloc(b, &dws, (size_t)nh * S * 2 * 132 * 4))) return r;
+  HIP_TRY(hipMemsetAsync(dout, 0, (size_t)S * Sq * 2, b.s));
+  PfVariant v;
+  v.pfv = pfv;
+  v.nw = nw;
+  v.split = split;
+  v.deep = deep;
+  v.split_min_s = 1;  // the size policy belongs to the product wrapper
+  launch_attn_prefill_variant(dq, dkc, dvc, dvtc, (u16*)dout, (float*)dws, S,
+                              pos0, nh, nkv, hd, max_seq, Sq, Sq, window, v,
+                              b.s);
+  HIP_TRY(hipGetLastError());
+  return ob_down16(b, (u16*)dout, (size_t)S * Sq, out);
+}
+
+extern "C" int cake_hip_op_attn_decode(int nh, int nkv, int hd, int max_seq,
+                                       int pos, int window, int nchunk,
+                                       int repeats, const float* q,
+                                       const float* kc, const float* vc,
+                                       float* out, int device) {
+  const char* who = "op_attn_decode";
+  int r = attn_geom_err(who, nh, nkv, hd, max_seq);
+  if (r) return r;
+  if (pos < 0 || pos + 1 > max_seq)
+    return set_err(5, "%s: pos %d outside the cache (max_seq %d)", who, pos,
+                   max_seq);
+  if (window < 0) return set_err(5, "%s: window %d < 0", who, window);
+  if (nchunk < 1 || nchunk > 64)
+    return set_err(5, "%s: nchunk %d outside [1,64]", who, nchunk);
+  if (repeats < 1 || repeats > 16)
+    return set_err(5, "%s: repeats %d outside [1,16]", who, repeats);
+  OpBufs b;
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreate(&b.s));
+  const int Sq = nh * hd;
+  const size_t ncache = (size_t)nkv * max_seq * hd;
+  u16 *dq, *dkc, *dvc;
+  void *dout, *dws, *dcnt, *dpos;
+  if ((r = ob_up16(b, q, Sq, &dq))) return r;
+  if ((r = ob_up16(b, kc, ncache, &dkc))) return r;
+  if ((r = ob_up16(b, vc, ncache, &dvc))) return r;
+  if ((r = ob_alloc(b, &dout, (size_t)repeats * Sq * 2))) return r;
+  if ((r = ob_alloc(b, &dws, (size_t)nh * 64 * (hd + 4) * 4))) return r;
+  if ((r = ob_alloc(b, &dcnt, (size_t)nh * 4))) return r;
+  if ((r = ob_upf32(b, &pos, sizeof(int), &dpos))) return r;
+  HIP_TRY(hipMemsetAsync(dout, 0, (size_t)repeats * Sq * 2, b.s));
+  // counters zeroed ONCE: the launches below share them back to back, as the
+  // product's decode loop does (epoch-free modulo election)
+  HIP_TRY(hipMemsetAsync(dcnt, 0, (size_t)nh * 4, b.s));
+  for (int i = 0; i < repeats; ++i)
+    launch_attn_decode(dq, dkc, dvc, (const int*)dpos, (float*)dws,
+                       (u32*)dcnt, (u16*)dout + (size_t)i * Sq, nh, nkv, hd,
+                       max_seq, nchunk, window, b.s);
+  HIP_TRY(hipGetLastError());
+  return ob_down16(b, (u16*)dout, (size_t)repeats * Sq, out);
+}
+
+// The launch choices the product makes for a shape, for the host-side
+// dispatch check: out = {pfv, nw, split, deep, split_min_s, decode grid_y}.
+extern "C" int cake_hip_attn_dispatch(int S, int nh, int nkv, int hd,
+                                      int out[6]) {
+  const PfVariant v = attn_prefill_policy(S, nh, hd);
+  out[0] = v.pfv;
+  out[1] = v.nw;
+  out[2] = v.split;
+  out[3] = v.deep;
+  out[4] = v.split_min_s;
+  out[5] = attn_decode_grid_y(nh, nkv, hd);
+  return 0;
+}
+
 // ---------------------------------------------------------------------------
 // stats / misc
 // ---------------------------------------------------------------------------

@@ -90,6 +90,23 @@ void launch_attn_prefill(const u16* qkv, const u16* kc, const u16* vc,
                          const u16* vtc, u16* out, float* ws, int S, int pos0,
                          int nh, int nkv, int hd, int max_seq, int qkv_stride,
                          int out_stride, int window, hipStream_t s);
+// Prefill-attention variant for hd == 128: pfv 1 = per-wave MFMA kernel,
+// >= 2 = LDS-staged kernel with nw (4|8) waves per block, optional split-KV
+// (+ combine pass, only when ws != nullptr and S >= split_min_s) or a deep
+// schedule (1|2, ignored under split).  Other head dims always run the
+// generic kernel.
+struct PfVariant {
+  int pfv = 2, nw = 8, split = 0, deep = 0, split_min_s = 1024;
+};
+// the variant the product picks for this shape (env knobs + size policy)
+PfVariant attn_prefill_policy(int S, int nh, int hd);
+// launch_attn_prefill == launch_attn_prefill_variant(attn_prefill_policy())
+void launch_attn_prefill_variant(const u16* qkv, const u16* kc,
+                                 const u16* vc, const u16* vtc, u16* out,
+                                 float* ws, int S, int pos0, int nh, int nkv,
+                                 int hd, int max_seq, int qkv_stride,
+                                 int out_stride, int window, PfVariant v,
+                                 hipStream_t s);
 void launch_rope_simple(u16* x, const float* cost, const float* sint, int bh,
                         int s, int d, hipStream_t st);
 void launch_argmax(const float* logits, int n, float* pval, int* pidx,

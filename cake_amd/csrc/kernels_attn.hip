@@ -133,7 +133,8 @@ __global__ void k_rope_store_prefill(u16* __restrict__ qkv,
 // positions into ws[h][chunk] = {o[hd], m, l}; the LAST-arriving block of a
 // head combines the partials (agent-scope release/acquire + arrival counter
 // per cdna_hip_programming.md §6 Guideline 16 — placement-independent).
-// cnt[nh] must be zeroed before every launch (hipMemsetAsync node).
+// cnt[nh] is zeroed once per chunk count, not per launch: the election is
+// modulo nchunk (tests/test_attn_ops_gpu.py repeats launches on one zeroing).
 // K/V row loads: 64 lanes x 4 B = one coalesced 256 B transaction.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_attn_decode_fused(
@@ -1501,10 +1502,9 @@ void launch_attn_decode(const u16* q, const u16* kc, const u16* vc,
                      q, kc, vc, pos, ws, cnt, out, nh, nkv, hd, max_seq,
                      nchunk, window);
 }
-void launch_attn_prefill(const u16* qkv, const u16* kc, const u16* vc,
-                         const u16* vtc, u16* out, float* ws, int S, int pos0,
-                         int nh, int nkv, int hd, int max_seq, int qkv_stride,
-                         int out_stride, int window, hipStream_t s) {
+// Product dispatch policy: the MFMA-prefill variant launch_attn_prefill
+// picks for (S, nh, hd), from the env knobs (read once) and the size rules.
+PfVariant attn_prefill_policy(int S, int nh, int hd) {
   static const int pfv =
       getenv("CAKE_PF_ATTN") ? atoi(getenv("CAKE_PF_ATTN")) : 2;
   static const int nw_env =
@@ -1519,19 +1519,43 @@ void launch_attn_prefill(const u16* qkv, const u16* kc, const u16* vc,
       getenv("CAKE_PF_SPLIT") ? atoi(getenv("CAKE_PF_SPLIT")) : 0;
   static const int deep_env =
       getenv("CAKE_PF_DEEP") ? atoi(getenv("CAKE_PF_DEEP")) : 0;
+  (void)hd;
+  // 128-row blocks whenever the 256-row grid can't give the scheduler
+  // >= 2 blocks/CU of backfill against the causal work skew
+  const bool nw4 = nw_env ? nw_env == 4
+                          : (long)((S + 255) / 256) * nh < 512;
+  PfVariant v;
+  v.pfv = pfv;
+  v.nw = nw4 ? 4 : 8;
+  v.split = split_env != 0;
+  v.deep = deep_env;
+  // split-KV halves every block's own tile range (the wall is the
+  // longest block); below S=1024 the extra combine launch costs more
+  // than the balance buys (launch-bound small models)
+  v.split_min_s = 1024;
+  return v;
+}
+void launch_attn_prefill(const u16* qkv, const u16* kc, const u16* vc,
+                         const u16* vtc, u16* out, float* ws, int S, int pos0,
+                         int nh, int nkv, int hd, int max_seq, int qkv_stride,
+                         int out_stride, int window, hipStream_t s) {
+  launch_attn_prefill_variant(qkv, kc, vc, vtc, out, ws, S, pos0, nh, nkv,
+                              hd, max_seq, qkv_stride, out_stride, window,
+                              attn_prefill_policy(S, nh, hd), s);
+}
+void launch_attn_prefill_variant(const u16* qkv, const u16* kc,
+                                 const u16* vc, const u16* vtc, u16* out,
+                                 float* ws, int S, int pos0, int nh, int nkv,
+                                 int hd, int max_seq, int qkv_stride,
+                                 int out_stride, int window, PfVariant v,
+                                 hipStream_t s) {
+  const int pfv = v.pfv;
   if (hd == 128 && pfv >= 2) {
     const size_t smem2 = 2 * 32 * 256 + 2 * 128 * 64;
     const size_t smem3 = 3 * 32 * 256 + 3 * 128 * 64;
-    // 128-row blocks whenever the 256-row grid can't give the scheduler
-    // >= 2 blocks/CU of backfill against the causal work skew
-    const bool nw4 = nw_env ? nw_env == 4
-                            : (long)((S + 255) / 256) * nh < 512;
-    // split-KV halves every block's own tile range (the wall is the
-    // longest block); below S=1024 the extra combine launch costs more
-    // than the balance buys (launch-bound small models)
-    const bool split = split_env != 0 && ws != nullptr && S >= 1024;
-    const int deep = (!split && (deep_env == 1 || deep_env == 2))
-                         ? deep_env : 0;
+    const bool nw4 = v.nw == 4;
+    const bool split = v.split && ws != nullptr && S >= v.split_min_s;
+    const int deep = (!split && (v.deep == 1 || v.deep == 2)) ? v.deep : 0;
     const int gz = split ? 2 : 1;
     if (nw4 && split)
       hipLaunchKernelGGL((k_attn_prefill_mfma2<4, 2, 0>),

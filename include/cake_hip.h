@@ -149,6 +149,46 @@ int cake_hip_op_rope(int b, int h, int s, int d, const float *x,
                      const float *cosv, const float *sinv, float *out,
                      int device);
 
+/* Attention + KV-store op entries (test-only).  Every call allocates
+ * buffers of exactly the engine's sizes, runs the real launch wrappers on a
+ * private stream and frees the buffers.  Arguments are validated before any
+ * device call (error 5): nh % nkv == 0; hd % 8 == 0, 8 <= hd <= 128;
+ * max_seq % 32 == 0; pos0 + S <= max_seq; 1 <= nchunk <= 64; the variant
+ * must be one the prefill dispatcher can express.
+ *
+ * kv_store: rope [+ per-head QK-norm] + cache store of S raw qkv rows
+ * (S, (nh+2*nkv)*hd) at positions pos0.. (decode != 0: the one-row decode
+ * kernel at position pos0).  cos/sin are (max_seq, hd/2) f32 tables;
+ * q_norm/k_norm are (hd) rows or both NULL.  kc/vc (nkv, max_seq, hd) and
+ * vtc (nkv, hd, max_seq) are IN/OUT host images; q_out (S, nh*hd) receives
+ * the roped q rows. */
+int cake_hip_op_kv_store(int S, int pos0, int decode, int nh, int nkv, int hd,
+                         int max_seq, const float *qkv, const float *cosv,
+                         const float *sinv, const float *q_norm,
+                         const float *k_norm, float eps, float *kc, float *vc,
+                         float *vtc, float *q_out, int device);
+/* Causal [sliding-window] GQA attention of S post-rope q rows (S, nh*hd) at
+ * positions pos0.. over the cache images; out (S, nh*hd).  Variant: hd 128
+ * takes pfv 1 (nw 8, no split/deep) or pfv 2 with nw 4|8 and at most one of
+ * split (0|1) / deep (0|1|2); any other hd takes {0,0,0,0} (generic
+ * kernel). */
+int cake_hip_op_attn_prefill(int S, int pos0, int nh, int nkv, int hd,
+                             int max_seq, int window, int pfv, int nw,
+                             int split, int deep, const float *q,
+                             const float *kc, const float *vc,
+                             const float *vtc, float *out, int device);
+/* Decode attention of one q row (nh*hd) at position pos, split over nchunk
+ * chunks.  The arrival counters are zeroed once, then the kernel is launched
+ * `repeats` (1..16) times back to back; out is (repeats, nh*hd). */
+int cake_hip_op_attn_decode(int nh, int nkv, int hd, int max_seq, int pos,
+                            int window, int nchunk, int repeats,
+                            const float *q, const float *kc, const float *vc,
+                            float *out, int device);
+/* Host only: the launch choices the product makes for a prefill of S rows and
+ * for decode at this head geometry: out = {pfv, nw, split, deep,
+ * split_min_s, decode grid_y (0 = per-head kernel)}. */
+int cake_hip_attn_dispatch(int S, int nh, int nkv, int hd, int out[6]);
+
 /* ---- observability (bench roofline evidence) ----------------------------
  * JSON {"kernels": {name: {"launches": n, "ms": t, "bytes": b}}} — per-
  * kernel-family hipEvent timing + algorithmic bytes, collected while
