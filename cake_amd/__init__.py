@@ -71,6 +71,11 @@ def _load_lib():
     lib.cake_hip_set_stats.argtypes = [p, c]
     lib.cake_hip_set_sampling.argtypes = [p, ctypes.c_float,
                                           ctypes.c_uint64]
+    lib.cake_hip_set_sampling_ex.argtypes = [p, f, c, f, f, c,
+                                             ctypes.c_uint64]
+    lib.cake_hip_op_sample.argtypes = [c, fp, f, c, f, f, u32p, c,
+                                       ctypes.c_uint64, c, c, u32p,
+                                       ctypes.POINTER(c), fp, c]
     lib.cake_hip_sync.argtypes = [p]
     return lib
 
@@ -238,6 +243,26 @@ def op_attn_decode(q, kc, vc, pos, window=0, nchunk=8, repeats=1, device=0):
     return out
 
 
+def op_sample(logits, temperature, top_k=0, top_p=1.0, repeat_penalty=1.0,
+              history=(), seed=299792458, first_draw=0, draws=1, device=0):
+    """The on-device sampler on f32 logits (V,): penalty over every id of
+    `history`, top-k, top-p, then `draws` consecutive seeded draws from
+    draw index first_draw.  Returns (tokens (draws,), kept, tau)."""
+    logits = np.ascontiguousarray(logits, dtype=np.float32)
+    _, lp = _f32_shaped(logits, (logits.size,), "logits")
+    hist = np.ascontiguousarray(history, dtype=np.uint32).reshape(-1)
+    toks = np.empty(max(int(draws), 1), dtype=np.uint32)
+    kept = ctypes.c_int()
+    thr = ctypes.c_float()
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    _check(_lib.cake_hip_op_sample(
+        logits.size, lp, temperature, int(top_k), top_p, repeat_penalty,
+        hist.ctypes.data_as(u32p) if hist.size else None, hist.size, seed,
+        int(first_draw), int(draws), toks.ctypes.data_as(u32p),
+        ctypes.byref(kept), ctypes.byref(thr), device))
+    return toks[:max(int(draws), 0)], kept.value, np.float32(thr.value)
+
+
 def attn_dispatch(S, nh, nkv, hd):
     """The product's launch choices for this shape (host only): dict with the
     prefill variant and the grouped-decode grid_y (0 = per-head kernel)."""
@@ -351,6 +376,17 @@ class Engine:
         text_model.rs:104); > 0 = on-GPU Gumbel-argmax sampling."""
         _check(_lib.cake_hip_set_sampling(
             self._h, ctypes.c_float(temperature), seed))
+
+    def set_sampling_ex(self, temperature, top_k=0, top_p=1.0,
+                        repeat_penalty=1.0, repeat_last_n=128,
+                        seed=299792458):
+        """set_sampling plus on-GPU top-k, top-p and cake's repeat penalty
+        (text_model.rs:433-452) inside the decode graph; semantics in
+        include/cake_hip.h.  All three off == set_sampling."""
+        _check(_lib.cake_hip_set_sampling_ex(
+            self._h, temperature, int(top_k or 0),
+            1.0 if top_p is None else top_p, repeat_penalty,
+            int(repeat_last_n), seed))
 
     def set_stats(self, enabled):
         _check(_lib.cake_hip_set_stats(self._h, 1 if enabled else 0))

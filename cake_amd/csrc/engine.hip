@@ -298,6 +298,13 @@ struct cake_engine {
   int nchunk = 8;   // split-KV chunks for decode attention (CAKE_NCHUNK)
   float inv_temp = 0.f;        // 0 = greedy ArgMax (text_model.rs:104)
   uint64_t sample_seed = 299792458ull;  // cake default seed (lib.rs:180)
+  // top-k / top-p / repeat penalty (cake_hip_set_sampling_ex); all off =
+  // the legacy launch_argmax path, untouched
+  bool sample_ex = false;
+  int top_k = 0, repeat_last_n = 0;
+  float top_p = 1.f, repeat_penalty = 1.f;
+  void* sample_mem = nullptr;  // backs sws (head engines, vocab permitting)
+  SampleWs sws{};
   int gu_rows = 4;  // gate_up channels per block (CAKE_GU_ROWS)
 
   hipStream_t stream = nullptr;
@@ -620,8 +627,15 @@ static void enqueue_head_sample(cake_engine* e, int S, int advance_by,
   }
   if (advance_by > 1)
     launch_advance_pos(e->dev_pos, advance_by - 1, e->stream);
-  {  // greedy ArgMax / Gumbel sampling + ring append + pos++
-     // (text_model.rs:102-118)
+  if (e->sample_ex) {  // penalty -> top-k -> top-p -> Gumbel-argmax, with
+                       // the same bookkeeping (text_model.rs:102-118,433-452)
+    StatScope ss(e, "sample", (double)V * 4 * 3, 0);
+    launch_sample(e->logits, V, e->sws, e->dev_tok, e->dev_pos, e->ring,
+                  e->dev_step, 1, e->inv_temp, e->top_k, e->top_p,
+                  e->repeat_penalty, e->repeat_last_n, 1, e->sample_seed,
+                  e->stream);
+  } else {  // greedy ArgMax / Gumbel sampling + ring append + pos++
+            // (text_model.rs:102-118)
     StatScope ss(e, "argmax", (double)V * 4, 0);
     launch_argmax(e->logits, V, e->pval, e->pidx, e->dev_tok, e->dev_pos,
                   e->ring, e->dev_step, 1, e->inv_temp, e->sample_seed,
@@ -786,6 +800,12 @@ extern "C" int cake_hip_engine_create(const char* config_json, int layer_lo,
   ALLOC(e->ring, u32, cake_engine::RING_CAP);
   ALLOC(e->pval, float, 256);
   ALLOC(e->pidx, int, 256);
+  if (e->has_head() && V >= 1 && V <= SAMPLE_MAX_V) {
+    const size_t sb = sample_ws_bytes(V);
+    ALLOC(e->sample_mem, char, sb);
+    HIP_TRY(hipMemset(e->sample_mem, 0, sb));
+    e->sws = sample_ws_bind(e->sample_mem, V);
+  }
   if (const char* nc = getenv("CAKE_NCHUNK")) {
     int v = atoi(nc);
     if (v >= 1 && v <= 64) e->nchunk = v;
@@ -856,6 +876,7 @@ extern "C" void cake_hip_engine_free(cake_engine* e) {
   hipFree(e->gu); hipFree(e->act); hipFree(e->logits); hipFree(e->fbuf);
   if (e->wscratch) hipFree(e->wscratch);
   hipFree(e->ids); hipFree(e->ring); hipFree(e->pval); hipFree(e->pidx);
+  if (e->sample_mem) hipFree(e->sample_mem);
   hipFree(e->attn_ws); hipFree(e->pf_ws); hipFree(e->attn_cnt);
   hipFree(e->gemv_ws); hipFree(e->gemv_cnt);
   if (e->nsq_part) { hipFree(e->nsq_part); hipFree(e->nsq_cnt);
@@ -1227,6 +1248,8 @@ extern "C" int cake_hip_reset(cake_engine* e) {
   HIP_TRY(hipMemset(e->dev_pos, 0, 4));
   HIP_TRY(hipMemset(e->dev_step, 0, 4));
   HIP_TRY(hipMemset(e->dev_tok, 0, 4));
+  // sampler history and draw counter start over with the sequence
+  if (e->sample_mem) HIP_TRY(hipMemset(e->sws.state, 0, 4 * 4));
   // clear the KV caches (Goodbye semantics, worker.rs:364-384 /
   // cache.rs:248-253)
   const size_t kv_bytes = (size_t)e->c.nkv * e->max_seq * e->c.hd() * 2;
@@ -2022,12 +2045,28 @@ extern "C" int cake_hip_attn_dispatch(int S, int nh, int nkv, int hd,
 // Sampling config (create_logits_processor, text_model.rs:102-118):
 // temperature <= 0 -> greedy ArgMax; > 0 -> Gumbel-argmax at that
 // temperature.  Changing it invalidates a captured decode graph.
-extern "C" int cake_hip_set_sampling(cake_engine* e, float temperature,
-                                     uint64_t seed) {
+static int apply_sampling(cake_engine* e, float temperature, int top_k,
+                          float top_p, float repeat_penalty,
+                          int repeat_last_n, uint64_t seed) {
+  const int V = e->c.vocab;
+  const bool k_on = top_k > 0 && top_k < V;
+  const bool p_on = top_p > 0.f && top_p < 1.f;
+  const bool pen_on = repeat_penalty != 1.f && repeat_last_n > 0;
+  const bool ex = pen_on || (temperature > 0.f && (k_on || p_on));
+  if (ex && !e->sample_mem)
+    return set_err(5, "top-k/top-p/repeat-penalty sampling needs the head "
+                   "on this engine and vocab <= %d", SAMPLE_MAX_V);
   HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(hipStreamSynchronize(e->stream));
   e->inv_temp = temperature > 0.f ? 1.0f / temperature : 0.f;
   e->sample_seed = seed;
+  e->top_k = top_k;
+  e->top_p = top_p;
+  e->repeat_penalty = repeat_penalty;
+  e->repeat_last_n = repeat_last_n;
+  e->sample_ex = ex;
+  // a new configuration starts a new draw sequence and an empty history
+  if (e->sample_mem) HIP_TRY(hipMemset(e->sws.state, 0, 4 * 4));
   if (e->graph) {
     hipGraphExecDestroy(e->graph);
     e->graph = nullptr;
@@ -2037,6 +2076,100 @@ extern "C" int cake_hip_set_sampling(cake_engine* e, float temperature,
     e->pf_graph = nullptr;
     e->pf_graph_S = -1;
   }
+  return 0;
+}
+extern "C" int cake_hip_set_sampling(cake_engine* e, float temperature,
+                                     uint64_t seed) {
+  return apply_sampling(e, temperature, 0, 1.f, 1.f, 0, seed);
+}
+static int sampling_args_err(const char* who, float temperature, float top_p,
+                             float repeat_penalty) {
+  if (std::isnan(temperature) || std::isnan(top_p) ||
+      std::isnan(repeat_penalty))
+    return set_err(5, "%s: NaN argument", who);
+  if (!(repeat_penalty > 0.f))
+    return set_err(5, "%s: repeat_penalty %g must be > 0", who,
+                   repeat_penalty);
+  return 0;
+}
+// The rest of create_logits_processor (text_model.rs:102-118) plus the
+// repeat penalty (text_model.rs:433-452), all on the device.  With every
+// option off this IS cake_hip_set_sampling(temperature, seed).
+extern "C" int cake_hip_set_sampling_ex(cake_engine* e, float temperature,
+                                        int top_k, float top_p,
+                                        float repeat_penalty,
+                                        int repeat_last_n, uint64_t seed) {
+  int r = sampling_args_err("set_sampling_ex", temperature, top_p,
+                            repeat_penalty);
+  if (r) return r;
+  if (repeat_last_n < 0 || repeat_last_n > SAMPLE_HIST_CAP)
+    return set_err(5, "set_sampling_ex: repeat_last_n %d outside [0,%d]",
+                   repeat_last_n, SAMPLE_HIST_CAP);
+  return apply_sampling(e, temperature, top_k, top_p, repeat_penalty,
+                        repeat_last_n, seed);
+}
+
+// Test-only: `draws` consecutive draw indices of the product's sampler on
+// private buffers and a private stream; the history stays as given.
+extern "C" int cake_hip_op_sample(int V, const float* logits,
+                                  float temperature, int top_k, float top_p,
+                                  float repeat_penalty,
+                                  const uint32_t* history, int n_history,
+                                  uint64_t seed, int first_draw, int draws,
+                                  uint32_t* tokens_out, int* kept_out,
+                                  float* thr_out, int device) {
+  const char* who = "op_sample";
+  int r = sampling_args_err(who, temperature, top_p, repeat_penalty);
+  if (r) return r;
+  if (V < 1 || V > SAMPLE_MAX_V)
+    return set_err(5, "%s: V %d outside [1,%d]", who, V, SAMPLE_MAX_V);
+  if (draws < 1 || draws > 8192)
+    return set_err(5, "%s: draws %d outside [1,8192]", who, draws);
+  if (first_draw < 0) return set_err(5, "%s: first_draw %d < 0", who,
+                                     first_draw);
+  if (n_history < 0 || n_history > SAMPLE_HIST_CAP)
+    return set_err(5, "%s: n_history %d outside [0,%d]", who, n_history,
+                   SAMPLE_HIST_CAP);
+  if (!logits || !tokens_out || !kept_out || !thr_out ||
+      (n_history > 0 && !history))
+    return set_err(5, "%s: null argument", who);
+  for (int i = 0; i < n_history; ++i)
+    if (history[i] >= (uint32_t)V)
+      return set_err(5, "%s: history id %u outside the vocabulary (%d)", who,
+                     history[i], V);
+  OpBufs b;
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreate(&b.s));
+  void *dl, *mem, *dtoks, *dmisc;
+  if ((r = ob_upf32(b, logits, (size_t)V * 4, &dl))) return r;
+  const size_t sb = sample_ws_bytes(V);
+  if ((r = ob_alloc(b, &mem, sb))) return r;
+  if ((r = ob_alloc(b, &dtoks, (size_t)draws * 4))) return r;
+  if ((r = ob_alloc(b, &dmisc, 3 * 4))) return r;  // tok, pos, step
+  HIP_TRY(hipMemsetAsync(mem, 0, sb, b.s));
+  HIP_TRY(hipMemsetAsync(dmisc, 0, 3 * 4, b.s));
+  SampleWs ws = sample_ws_bind(mem, V);
+  const u32 st[2] = {(u32)n_history, (u32)first_draw};
+  if (n_history > 0)
+    HIP_TRY(hipMemcpyAsync(ws.hist, history, (size_t)n_history * 4,
+                           hipMemcpyHostToDevice, b.s));
+  HIP_TRY(hipMemcpyAsync(ws.state, st, sizeof st, hipMemcpyHostToDevice,
+                         b.s));
+  const float inv_temp = temperature > 0.f ? 1.0f / temperature : 0.f;
+  u32* misc = (u32*)dmisc;
+  for (int d = 0; d < draws; ++d)
+    launch_sample((const float*)dl, V, ws, misc, (int*)(misc + 1),
+                  (u32*)dtoks, (int*)(misc + 2), 0, inv_temp, top_k, top_p,
+                  repeat_penalty, n_history, 0, seed, b.s);
+  HIP_TRY(hipGetLastError());
+  u32 res[4];
+  HIP_TRY(hipMemcpyAsync(tokens_out, dtoks, (size_t)draws * 4,
+                         hipMemcpyDeviceToHost, b.s));
+  HIP_TRY(hipMemcpyAsync(res, ws.state, sizeof res, hipMemcpyDeviceToHost,
+                         b.s));
+  HIP_TRY(hipStreamSynchronize(b.s));
+  *kept_out = (int)res[2];
+  memcpy(thr_out, &res[3], 4);
   return 0;
 }
 

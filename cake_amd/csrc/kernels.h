@@ -113,6 +113,32 @@ void launch_argmax(const float* logits, int n, float* pval, int* pidx,
                    u32* tok, int* pos, u32* ring, int* step, int advance_pos,
                    float inv_temp, uint64_t seed, hipStream_t s);
 void launch_advance_pos(int* pos, int by, hipStream_t s);
+// On-device top-k / top-p / repeat-penalty sampler (kernels_sample.hip).
+// One device allocation of sample_ws_bytes(V), carved by sample_ws_bind;
+// hist / state persist across steps and must start zeroed.
+constexpr int SAMPLE_HIST_CAP = 1024;  // history ring capacity (power of 2)
+constexpr int SAMPLE_MAX_V = 1 << 18;  // block spans and u64 masses fit
+struct SampleWs {
+  unsigned long long* hmass;  // [6][2048] fixed-point mass histograms
+  u32* hcnt;                  // [6][2048] count histograms
+  void* sel;                  // selection state entering each pass
+  float* work;                // [V] penalised logits (the raw ones stay raw)
+  float *pmax, *pmin, *pval;  // [128] per-block partials
+  int* pidx;
+  u32* hist;   // ring of the last sampled ids
+  u32* state;  // {history count, draw counter, kept, tau bits}
+};
+size_t sample_ws_bytes(int V);
+SampleWs sample_ws_bind(void* base, int V);
+// penalty (over the last `last_n` history ids) -> top-k -> top-p -> seeded
+// Gumbel-argmax at draw index state[1] (inv_temp == 0: argmax), then the
+// bookkeeping of launch_argmax; the token joins the history ring when
+// advance_hist.  3 launches, +3 per active select.  V <= SAMPLE_MAX_V.
+void launch_sample(const float* logits, int V, const SampleWs& b, u32* tok,
+                   int* pos, u32* ring, int* step, int advance_pos,
+                   float inv_temp, int top_k, float top_p, float penalty,
+                   int last_n, int advance_hist, uint64_t seed,
+                   hipStream_t s);
 void launch_gemm(const u16* A, const u16* W, u16* C, const u16* res, int M,
                  int N, int K, int epi, hipStream_t s);
 // hipBLASLt path for the plain prefill GEMMs (gemm_lib.hip); false => caller

@@ -9,10 +9,12 @@ Mirrors cake's API surface (cake-core/src/cake/sharding/api/mod.rs:66-110):
 Generation is the same hot loop the bench measures (Master::generate_text,
 master.rs:109-171): greedy ArgMax when temperature <= 0, on-GPU
 Gumbel-argmax sampling for plain temperature (cake's own
-temperature-sampling trick, text_model.rs:102-118).  top_k/top_p requests
-take a host-sampling loop over per-token logits — faithfully mirroring
-cake, whose LogitsProcessor (candle Sampling::TopK/TopP/TopKThenTopP,
-created at text_model.rs:102-118) also samples on the host.
+temperature-sampling trick, text_model.rs:102-118).  top_k / top_p /
+repeat_penalty / repeat_last_n requests stay on that loop too: the engine's
+set_sampling_ex runs the penalty (text_model.rs:433-452), the top-k and
+top-p selection and the seeded draw on the GPU inside the decode graph.
+Only an engine without set_sampling_ex falls back to the host-sampling loop
+over per-token logits (one append-prefill and one logits copy per token).
 
 Tokenization: pass a `tokenizers.Tokenizer` (tokenizer.json) for text
 prompts; without one, requests supply `prompt_token_ids` directly (the
@@ -63,6 +65,17 @@ def sample_from_logits(logits, temperature, top_k, top_p, rng):
     return int(rng.choice(order, p=kept))
 
 
+def apply_repeat_penalty(logits, penalty, ids):
+    """cake's sign-aware repeat penalty (text_model.rs:51-99): each unique
+    id is scaled once, l / penalty if l >= 0 else l * penalty."""
+    out = np.array(logits, dtype=np.float32)
+    idx = np.unique(np.asarray(ids, dtype=np.int64))
+    v = out[idx]
+    out[idx] = np.where(v >= 0, v * np.float32(1.0 / penalty),
+                        v * np.float32(penalty))
+    return out
+
+
 class GenSession:
     """Thin generation driver over an Engine-compatible object.
 
@@ -100,18 +113,27 @@ class GenSession:
                     return
 
     def generate_sampled(self, prompt_ids, max_tokens, temperature, top_k,
-                         top_p, seed):
-        """Host-sampling loop for top-k/top-p: per-token logits from
-        append-prefill steps, sampled like cake's host-side
-        LogitsProcessor (slower than the graph-replayed decode loop, same
-        trade cake makes)."""
+                         top_p, seed, repeat_penalty=1.0, repeat_last_n=0):
+        """Host-sampling fallback for engines without set_sampling_ex:
+        per-token logits from append-prefill steps, sampled like cake's
+        host-side LogitsProcessor (far slower than the graph-replayed
+        decode loop).  The repeat penalty covers generated tokens only."""
         self.engine.reset()
         rng = np.random.default_rng(seed)
         _, logits = self.engine.prefill(
             np.asarray(prompt_ids, dtype=np.uint32), want_logits=True)
         produced = 0
+        history = []
         while True:
-            tok = sample_from_logits(logits, temperature, top_k, top_p, rng)
+            if repeat_penalty != 1.0 and repeat_last_n > 0 and history:
+                logits = apply_repeat_penalty(logits, repeat_penalty,
+                                              history[-repeat_last_n:])
+            if temperature > 0:
+                tok = sample_from_logits(logits, temperature, top_k, top_p,
+                                         rng)
+            else:
+                tok = int(np.argmax(logits))
+            history.append(tok)
             yield tok
             produced += 1
             if produced >= max_tokens or tok in self.eos_ids:
@@ -165,8 +187,15 @@ def create_app(engine, model_name="cake-amd", tokenizer=None, eos_ids=(),
         top_k = body.get("top_k")
         top_p = body.get("top_p")
         seed = int(body.get("seed", 299792458))
-        use_host_sampling = temperature > 0 and (top_k or
-                                                 (top_p and top_p < 1.0))
+        repeat_penalty = float(body.get("repeat_penalty", 1.0))
+        # the engine's history ring holds 1024 ids
+        repeat_last_n = max(0, min(1024, int(body.get("repeat_last_n", 128))))
+        wants_ex = bool(
+            (temperature > 0 and (top_k or (top_p and top_p < 1.0))) or
+            (repeat_penalty != 1.0 and repeat_last_n > 0))
+        # on the device when the engine can; else the host loop
+        on_device = wants_ex and hasattr(engine, "set_sampling_ex")
+        use_host_sampling = wants_ex and not on_device
         if "prompt_token_ids" in body:
             ids = [int(t) for t in body["prompt_token_ids"]]
         elif kind == "chat":
@@ -181,11 +210,20 @@ def create_app(engine, model_name="cake-amd", tokenizer=None, eos_ids=(),
             the first engine call until exhaustion (or client disconnect —
             GeneratorExit releases it through the `with`)."""
             with engine_lock:
-                if not use_host_sampling and hasattr(engine, "set_sampling"):
+                if on_device:
+                    engine.set_sampling_ex(
+                        temperature, top_k=int(top_k or 0),
+                        top_p=float(top_p) if top_p else 1.0,
+                        repeat_penalty=repeat_penalty,
+                        repeat_last_n=repeat_last_n, seed=seed)
+                elif (not use_host_sampling and
+                      hasattr(engine, "set_sampling")):
                     engine.set_sampling(temperature, seed)
                 if use_host_sampling:
-                    gen = sess.generate_sampled(ids, max_tokens, temperature,
-                                                top_k, top_p, seed)
+                    gen = sess.generate_sampled(
+                        ids, max_tokens, temperature, top_k, top_p, seed,
+                        repeat_penalty=repeat_penalty,
+                        repeat_last_n=repeat_last_n)
                 else:
                     gen = sess.generate(ids, max_tokens)
                 for tok in gen:

@@ -200,6 +200,43 @@ int cake_hip_kernel_stats(cake_engine *e, char *buf, int cap);
  * temperature (the on-GPU sampling trick cake uses, text_model.rs:108-111).
  * The noise stream is seeded and deterministic per (seed, step). */
 int cake_hip_set_sampling(cake_engine *e, float temperature, uint64_t seed);
+/* The rest of create_logits_processor (text_model.rs:102-118: TopK, TopP,
+ * TopKThenTopP) and the repeat penalty the reference applies before every
+ * sample (text_model.rs:433-452, helper :51-99; defaults 1.1 over the last
+ * 128 tokens, lib.rs:193-198), all on the device and inside the decode and
+ * prefill graphs:
+ *   1. penalty: every unique id among the last repeat_last_n SAMPLED tokens
+ *      (prompt tokens never count) gets l * (1/penalty) if l >= 0, else
+ *      l * penalty; off when penalty == 1 or repeat_last_n == 0
+ *   2. top-k: keep the k largest; off when top_k <= 0 or >= vocab
+ *   3. top-p: among those, softmax at `temperature`, keep the minimal
+ *      descending prefix whose mass reaches top_p; off when <= 0 or >= 1
+ *   4. seeded Gumbel-argmax over the kept set; temperature <= 0 is the
+ *      argmax of the penalised logits (top-k / top-p moot)
+ * Tie rule: every entry equal to the boundary value of step 2 or 3 is kept,
+ * so the kept set is { l' >= tau } and may exceed k on exact f32 ties.
+ * The noise is indexed by a persistent draw counter that, like the history,
+ * advances on every sampled token (prefill's included) and is cleared by
+ * cake_hip_reset and by either setter.  Logits returned by cake_hip_prefill
+ * stay unpenalised.  With all three options off this call IS
+ * cake_hip_set_sampling(temperature, seed); cake_hip_set_sampling switches
+ * them off again.  Error 5: repeat_last_n outside [0,1024], repeat_penalty
+ * <= 0, NaN arguments, or an engine without the head / vocab > 2^18. */
+int cake_hip_set_sampling_ex(cake_engine *e, float temperature, int top_k,
+                             float top_p, float repeat_penalty,
+                             int repeat_last_n, uint64_t seed);
+/* Test-only: the sampler's launch wrapper on private buffers and a private
+ * stream.  Runs `draws` (1..8192) consecutive draw indices from first_draw
+ * on the same logits (V <= 2^18) and the same history (n_history <= 1024
+ * ids < V, all of them penalised); tokens_out[draws], *kept_out = size of
+ * the kept set, *thr_out = tau, the smallest kept penalised logit.
+ * Arguments are validated before any device call (error 5). */
+int cake_hip_op_sample(int V, const float *logits, float temperature,
+                       int top_k, float top_p, float repeat_penalty,
+                       const uint32_t *history, int n_history,
+                       uint64_t seed, int first_draw, int draws,
+                       uint32_t *tokens_out, int *kept_out, float *thr_out,
+                       int device);
 int cake_hip_stats_reset(cake_engine *e);
 int cake_hip_set_stats(cake_engine *e, int enabled);
 
