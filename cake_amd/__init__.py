@@ -66,6 +66,22 @@ def _load_lib():
     lib.cake_hip_op_attn_prefill.argtypes = [c] * 11 + [fp] * 5 + [c]
     lib.cake_hip_op_attn_decode.argtypes = [c] * 8 + [fp] * 4 + [c]
     lib.cake_hip_attn_dispatch.argtypes = [c, c, c, c, ctypes.POINTER(c)]
+    u8p = ctypes.POINTER(ctypes.c_uint8)
+    lib.cake_hip_op_gemv.argtypes = [c] * 7 + [fp, fp, u8p, fp, fp, fp, f, c,
+                                               u32p, fp, fp, fp, c]
+    lib.cake_hip_op_gemv_gateup.argtypes = [c, c, c, c, fp, fp, u8p, fp, fp,
+                                            f, fp, fp, c]
+    lib.cake_hip_op_gemv_qkv_rope.argtypes = [c] * 6 + [fp, fp, f] + \
+        [fp] * 7 + [c]
+    lib.cake_hip_op_gemm.argtypes = [c] * 6 + [fp, fp, fp, fp,
+                                               ctypes.POINTER(c), c]
+    lib.cake_hip_op_dequant_fp8.argtypes = [c, c, u8p, fp, fp, c]
+    lib.cake_hip_op_silu_mul_rows.argtypes = [c, c, fp, fp, c]
+    lib.cake_hip_op_rms_norm_rows.argtypes = [c, c, ctypes.c_long, c, f,
+                                              ctypes.c_long, fp, fp, fp, c]
+    lib.cake_hip_linear_dispatch.argtypes = [c, c, c, c, c,
+                                             ctypes.POINTER(c)]
+    lib.cake_hip_decode_dispatch.argtypes = [cp, ctypes.POINTER(c)]
     lib.cake_hip_kernel_stats.argtypes = [p, ctypes.c_char_p, c]
     lib.cake_hip_stats_reset.argtypes = [p]
     lib.cake_hip_set_stats.argtypes = [p, c]
@@ -270,6 +286,217 @@ def attn_dispatch(S, nh, nkv, hd):
     _check(_lib.cake_hip_attn_dispatch(S, nh, nkv, hd, o))
     return dict(pfv=o[0], nw=o[1], split=o[2], deep=o[3], split_min_s=o[4],
                 decode_grid_y=o[5])
+
+
+# ---- linear-layer op entries (GEMV / fp8 / GEMM) --------------------------
+OP_GUARD = 16                # guard elements behind every output buffer
+OP_SENTINEL = -2.0 ** 60     # what outputs and guards are pre-filled with
+GEMV_KINDS = {"bf16": 0, "fp8": 1, "splitk": 2}
+GEMM_VARIANTS = {"128": 0, "256": 1, "128x256": 2, "256p": 3, "library": 4}
+LINEAR_FAMILIES = ("gemv_reg", "gemv_stream", "gemv_fp8", "gemv_fp8_stream",
+                   "gateup", "gateup_fp8", "qkv_rope", "splitk", "gemm")
+LINEAR_KINDS = {"plain": 0, "gateup": 1, "qkv_rope": 2, "splitk": 3,
+                "gemm": 4}
+
+
+def _opt_f32(a, shape, name):
+    if a is None:
+        return None, None
+    return _f32_shaped(a, shape, name)
+
+
+def _u8(a, shape, name):
+    a = np.ascontiguousarray(a, dtype=np.uint8)
+    if a.shape != tuple(shape):
+        raise ValueError(f"{name}: shape {a.shape}, expected {tuple(shape)}")
+    return a, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
+
+
+def op_gemv(x, w, kind="bf16", sc=None, epi=0, res=None, nw=None, eps=1e-5,
+            rows=0, alias=False, chain=0, cnt_init=None, scale_in=None,
+            device=0):
+    """One GEMV launcher (kind bf16 | fp8 | splitk) on x (repeats, K) [and
+    res (repeats, N)], launched once per row back to back on counters set
+    once from cnt_init.  w (N, K) is bf16-exact f32, or uint8 e4m3fn codes
+    with sc (N/128, K/128).  chain 1 = norm-chain produce (cnt_init: 9
+    words), 2 = consume (scale_in, nw).  Returns (out (repeats, N), guards
+    (repeats, OP_GUARD), scale_out (repeats,) or None)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    x = x[None] if x.ndim == 1 else x
+    repeats, K = x.shape
+    N = w.shape[0]
+    k = GEMV_KINDS[kind]
+    _, xp = _f32_shaped(x, (repeats, K), "x")
+    wf = wfp = w8 = w8p = scp = None
+    if k == 1:
+        w8, w8p = _u8(w, (N, K), "w")
+        _s, scp = _f32_shaped(sc, (N // 128, K // 128), "sc")
+    else:
+        wf, wfp = _f32_shaped(w, (N, K), "w")
+    _r, rp = _opt_f32(res, (repeats, N), "res")
+    _n, nwp = _opt_f32(nw, (K,), "nw")
+    ci = cip = None
+    if cnt_init is not None:
+        ci = np.ascontiguousarray(
+            np.broadcast_to(np.asarray(cnt_init, dtype=np.uint32), (9,)))
+        cip = ci.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
+    si = sip = None
+    if scale_in is not None:
+        si, sip = _f32_shaped(np.float32(scale_in).reshape(1), (1,),
+                              "scale_in")
+    so = np.empty(repeats, dtype=np.float32) if chain == 1 else None
+    out = np.empty((repeats, N + OP_GUARD), dtype=np.float32)
+    fpp = ctypes.POINTER(ctypes.c_float)
+    _check(_lib.cake_hip_op_gemv(
+        k, N, K, epi, rows, 1 if alias else 0, repeats, xp, wfp, w8p, scp,
+        rp, nwp, eps, chain, cip, sip,
+        so.ctypes.data_as(fpp) if so is not None else None,
+        out.ctypes.data_as(fpp), device))
+    return out[:, :N], out[:, N:], so
+
+
+def op_gemv_gateup(x, w, I, sc=None, nw=None, eps=1e-5, rows=0,
+                   scale_in=None, device=0):
+    """Fused [norm ->] gate-up GEMV -> silu_mul on x (K,), w (2I, K) bf16-
+    exact f32 or uint8 fp8 codes with sc (2I/128, K/128).  Returns (out (I,),
+    guards)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    K = x.shape[0]
+    fp8 = sc is not None
+    _, xp = _f32_shaped(x, (K,), "x")
+    wfp = w8p = scp = None
+    if fp8:
+        _w, w8p = _u8(w, (2 * I, K), "w")
+        _s, scp = _f32_shaped(sc, (2 * I // 128, K // 128), "sc")
+    else:
+        _w, wfp = _f32_shaped(w, (2 * I, K), "w")
+    _n, nwp = _opt_f32(nw, (K,), "nw")
+    si = sip = None
+    if scale_in is not None:
+        si, sip = _f32_shaped(np.float32(scale_in).reshape(1), (1,),
+                              "scale_in")
+    out = np.empty(I + OP_GUARD, dtype=np.float32)
+    _check(_lib.cake_hip_op_gemv_gateup(
+        1 if fp8 else 0, I, K, rows, xp, wfp, w8p, scp, nwp, eps, sip,
+        out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), device))
+    return out[:I], out[I:]
+
+
+def op_gemv_qkv_rope(x, nw, w, cos, sin, kc, vc, vtc, pos, nh, nkv,
+                     eps=1e-5, device=0):
+    """The fused norm -> qkv GEMV -> rope -> KV-store decode kernel.  kc/vc
+    (nkv, max_seq, hd), vtc (nkv, hd, max_seq) are the PRIOR images.  Returns
+    (roped q (nh, hd), rest of the activation row incl. guards, kc, vc,
+    vtc)."""
+    kc = np.array(kc, dtype=np.float32, order="C")
+    nkv_, max_seq, hd = kc.shape
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    K = x.shape[0]
+    Nq = (nh + 2 * nkv) * hd
+    _, xp = _f32_shaped(x, (K,), "x")
+    _n, nwp = _f32_shaped(nw, (K,), "nw")
+    _w, wp = _f32_shaped(w, (Nq, K), "w")
+    _c, cp = _f32_shaped(cos, (max_seq, hd // 2), "cos")
+    _s, sp = _f32_shaped(sin, (max_seq, hd // 2), "sin")
+    kc, kp = _f32_shaped(kc, (nkv, max_seq, hd), "kc")
+    vc, vp = _f32_shaped(np.array(vc, dtype=np.float32, order="C"),
+                         (nkv, max_seq, hd), "vc")
+    vtc, vtp = _f32_shaped(np.array(vtc, dtype=np.float32, order="C"),
+                           (nkv, hd, max_seq), "vtc")
+    out = np.empty(Nq + OP_GUARD, dtype=np.float32)
+    _check(_lib.cake_hip_op_gemv_qkv_rope(
+        nh, nkv, hd, max_seq, pos, K, xp, nwp, eps, wp, cp, sp, kp, vp, vtp,
+        out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), device))
+    return out[:nh * hd].reshape(nh, hd), out[nh * hd:], kc, vc, vtc
+
+
+def op_gemm(a, w, variant, res=None, alias=False, device=0):
+    """a (M,K) @ w (N,K)^T [+ res (M,N)] by an explicit variant (a key of
+    GEMM_VARIANTS).  Returns (out (M,N), guards, ran): ran is the variant
+    name, or None when the library rejected the shape."""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    M, K = a.shape
+    N = w.shape[0]
+    _, ap = _f32_shaped(a, (M, K), "a")
+    _w, wp = _f32_shaped(w, (N, K), "w")
+    _r, rp = _opt_f32(res, (M, N), "res")
+    out = np.empty(M * N + OP_GUARD, dtype=np.float32)
+    ran = ctypes.c_int(-2)
+    _check(_lib.cake_hip_op_gemm(
+        GEMM_VARIANTS[variant], M, N, K, 0 if res is None else 1,
+        1 if alias else 0, ap, wp, rp,
+        out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+        ctypes.byref(ran), device))
+    name = None if ran.value < 0 else list(GEMM_VARIANTS)[ran.value]
+    return out[:M * N].reshape(M, N), out[M * N:], name
+
+
+def op_dequant_fp8(w8, sc, device=0):
+    """Blockwise fp8 -> bf16 dequant of w8 (N,K) uint8 with sc (N/128,
+    K/128).  Returns (out (N,K), guards)."""
+    w8 = np.ascontiguousarray(w8, dtype=np.uint8)
+    N, K = w8.shape
+    _, wp = _u8(w8, (N, K), "w8")
+    _s, scp = _f32_shaped(sc, (N // 128, K // 128), "sc")
+    out = np.empty(N * K + OP_GUARD, dtype=np.float32)
+    _check(_lib.cake_hip_op_dequant_fp8(
+        N, K, wp, scp, out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+        device))
+    return out[:N * K].reshape(N, K), out[N * K:]
+
+
+def op_silu_mul_rows(gu, device=0):
+    """Prefill silu_mul on gu (S, 2I) = [gate | up].  Returns (out (S, I),
+    guards)."""
+    gu = np.ascontiguousarray(gu, dtype=np.float32)
+    S, I = gu.shape[0], gu.shape[1] // 2
+    _, gp = _f32_shaped(gu, (S, 2 * I), "gu")
+    out = np.empty(S * I + OP_GUARD, dtype=np.float32)
+    _check(_lib.cake_hip_op_silu_mul_rows(
+        S, I, gp, out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), device))
+    return out[:S * I].reshape(S, I), out[S * I:]
+
+
+def op_rms_norm_rows(x, w, outer, inner, outer_stride, eps=1e-5, device=0):
+    """rms_norm of outer*inner rows of len(w) elements inside the flat buffer
+    x; row r starts at (r // inner) * outer_stride + (r % inner) * cols.
+    Returns (out, same flat layout with sentinels between the rows,
+    guards)."""
+    x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    _, xp = _f32_shaped(x, (x.size,), "x")
+    _w, wp = _f32_shaped(w, (w.size,), "w")
+    out = np.empty(x.size + OP_GUARD, dtype=np.float32)
+    _check(_lib.cake_hip_op_rms_norm_rows(
+        outer, inner, outer_stride, w.size, eps, x.size, xp, wp,
+        out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), device))
+    return out[:x.size], out[x.size:]
+
+
+def linear_dispatch(kind, n, K, M=1, fp8=False):
+    """The product's kernel choice for a linear layer (host only).  kind is a
+    key of LINEAR_KINDS; n = N (or I for gateup).  Returns dict(family, rows,
+    kb (0 = streaming kernel), lib_first, variant)."""
+    o = (ctypes.c_int * 5)()
+    _check(_lib.cake_hip_linear_dispatch(LINEAR_KINDS[kind], n, K, M,
+                                         1 if fp8 else 0, o))
+    d = dict(family=LINEAR_FAMILIES[o[0]], rows=o[1], kb=o[2])
+    if kind == "gemm":
+        d = dict(family="gemm", lib_first=bool(o[3]),
+                 variant=list(GEMM_VARIANTS)[o[4]])
+    return d
+
+
+def decode_dispatch(config):
+    """The five linear launches of one decode step of a model (host only), by
+    the engine's own predicates: {layer: (family, rows, kb)} for qkv, o,
+    gateup, down, head."""
+    if isinstance(config, dict):
+        config = json.dumps(config)
+    o = (ctypes.c_int * 15)()
+    _check(_lib.cake_hip_decode_dispatch(config.encode(), o))
+    return {k: (LINEAR_FAMILIES[o[3 * i]], o[3 * i + 1], o[3 * i + 2])
+            for i, k in enumerate(("qkv", "o", "gateup", "down", "head"))}
 
 
 def comm_id() -> bytes:

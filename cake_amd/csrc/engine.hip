@@ -402,6 +402,13 @@ static void stats_flush(cake_engine* e) {
   e->st.pool_used = 0;
 }
 
+// Full-rotation models without qk-norm and without fp8 weights take the
+// fused rms_norm -> qkv GEMV -> rope -> KV-store kernel (the QK-norm rows
+// exist exactly when c.qk_norm).  Shared with cake_hip_decode_dispatch.
+static bool fused_qkv_rope_applies(const ModelConfig& c) {
+  return !c.fp8 && !c.qk_norm && c.hd() % 4 == 0 && c.nqkv() % 4 == 0;
+}
+
 // ---------------------------------------------------------------------------
 // per-layer decode / prefill enqueue (the Transformer::forward sequence,
 // transformer.rs:103-135 + attention.rs:152-357 + mlp.rs:21-31)
@@ -415,7 +422,7 @@ static void enqueue_layer_decode(cake_engine* e, LayerDev& l,
   // rms_norm -> qkv GEMV -> rope -> KV-store kernel: one launch instead of
   // two, with the rope applied to the dot-product sums in LDS.
   const bool fused_qkv_rope =
-      !c.fp8 && !l.qnorm && !l.knorm && hd % 4 == 0 && (Nq % 4) == 0;
+      fused_qkv_rope_applies(c) && !l.qnorm && !l.knorm;
   if (fused_qkv_rope) {
     double wb = (double)Nq * H * 2;
     StatScope ss(e, "gemv_qkv", wb + 2.0 * H * 2 + Nq * 2, 2.0 * Nq * H);
@@ -810,10 +817,7 @@ extern "C" int cake_hip_engine_create(const char* config_json, int layer_lo,
     int v = atoi(nc);
     if (v >= 1 && v <= 64) e->nchunk = v;
   }
-  if (const char* gr = getenv("CAKE_GU_ROWS")) {
-    int v = atoi(gr);
-    if (v == 4 || v == 8) e->gu_rows = v;
-  }
+  e->gu_rows = gemv_gateup_rows_policy();  // CAKE_GU_ROWS
   ALLOC(e->attn_ws, float, (size_t)c.nh * 64 * (hd + 4));  // nchunk <= 64; row stride 132 f32 = 16B-aligned
   if (hd == 128 && e->bt >= 1024)  // split-KV prefill partials
     ALLOC(e->pf_ws, float, (size_t)c.nh * e->bt * 2 * 132);
@@ -2036,6 +2040,479 @@ extern "C" int cake_hip_attn_dispatch(int S, int nh, int nkv, int hd,
   out[3] = v.deep;
   out[4] = v.split_min_s;
   out[5] = attn_decode_grid_y(nh, nkv, hd);
+  return 0;
+}
+
+// ---- linear op entries (GEMV / fp8 / GEMM) ---------------------------------
+// Same conventions as the attention entries.  Every output buffer carries
+// CAKE_HIP_OP_GUARD extra elements past its end and is pre-filled with
+// CAKE_HIP_OP_SENTINEL; the guards come back with the output so a test sees
+// an out-of-range store or an element no block wrote.
+static const int OPG = CAKE_HIP_OP_GUARD;
+static int ob_sent16(OpBufs& b, size_t n, u16** dst) {
+  void* d = nullptr;
+  int r = ob_alloc(b, &d, n * 2);
+  if (r) return r;
+  *dst = (u16*)d;
+  launch_fill_const(*dst, n, CAKE_HIP_OP_SENTINEL, b.s);
+  return 0;
+}
+static int ob_sent32(OpBufs& b, size_t n, float** dst) {
+  std::vector<float> h(n, CAKE_HIP_OP_SENTINEL);
+  void* d = nullptr;
+  int r = ob_upf32(b, h.data(), n * 4, &d);
+  if (r) return r;
+  HIP_TRY(hipStreamSynchronize(b.s));  // h dies with this frame
+  *dst = (float*)d;
+  return 0;
+}
+static int ob_downf32(OpBufs& b, const void* src, size_t bytes, void* dst) {
+  HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, b.s));
+  HIP_TRY(hipStreamSynchronize(b.s));
+  return 0;
+}
+static int fp8_shape_err(const char* who, int N, int K) {
+  if (N < 128 || K < 128 || N % 128 != 0 || K % 128 != 0)
+    return set_err(5, "%s: fp8 weights need N %% 128 == 0 and K %% 128 == 0 "
+                   "(got %d x %d)", who, N, K);
+  return 0;
+}
+
+extern "C" int cake_hip_op_gemv(int kind, int N, int K, int epi, int rows,
+                                int alias, int repeats, const float* x,
+                                const float* w, const uint8_t* w8,
+                                const float* sc, const float* res,
+                                const float* nw, float eps, int chain,
+                                const uint32_t* cnt_init,
+                                const float* scale_in, float* scale_out,
+                                float* out, int device) {
+  const char* who = "op_gemv";
+  if (kind < 0 || kind > 2) return set_err(5, "%s: kind %d", who, kind);
+  if (N < 1) return set_err(5, "%s: N %d < 1", who, N);
+  if (K < 8 || K % 8 != 0)
+    return set_err(5, "%s: K must be a positive multiple of 8 (got %d)", who,
+                   K);
+  if (repeats < 1 || repeats > 16)
+    return set_err(5, "%s: repeats %d outside [1,16]", who, repeats);
+  if (epi < 0 || epi > 2) return set_err(5, "%s: epi %d", who, epi);
+  if (!x || !out) return set_err(5, "%s: x and out are required", who);
+  if (kind == 1) {
+    int r = fp8_shape_err(who, N, K);
+    if (r) return r;
+    if (!w8 || !sc) return set_err(5, "%s: fp8 needs w8 and sc", who);
+    if (rows != 0 && rows != 4 && rows != 8)
+      return set_err(5, "%s: fp8 rows %d not in {0,4,8}", who, rows);
+  } else {
+    if (!w) return set_err(5, "%s: bf16 needs w", who);
+    if (kind == 0 && rows != 0 && rows != 1 && rows != 2 && rows != 4 &&
+        rows != 8)
+      return set_err(5, "%s: rows %d not in {0,1,2,4,8}", who, rows);
+  }
+  if (kind == 2) {
+    if (K % 16 != 0)
+      return set_err(5, "%s: split-K needs K %% 16 == 0 (got %d)", who, K);
+    if (epi != 1 || nw || rows != 0 || chain)
+      return set_err(5, "%s: split-K is the residual epilogue only (epi 1, "
+                     "no norm, no rows override, no chain)", who);
+    if (!cnt_init) return set_err(5, "%s: split-K needs cnt_init", who);
+  }
+  if (nw && K > 16384)
+    return set_err(5, "%s: the streaming kernels (K > 16384) have no norm",
+                   who);
+  if ((epi == 1) != (res != nullptr))
+    return set_err(5, "%s: res goes with epi 1", who);
+  if (alias && epi != 1)
+    return set_err(5, "%s: alias needs the residual epilogue", who);
+  if (chain < 0 || chain > 2 || (chain && kind != 1))
+    return set_err(5, "%s: the norm chain is fp8 only (chain %d)", who,
+                   chain);
+  if (chain == 1 && (epi != 1 || !cnt_init || !scale_out || nw))
+    return set_err(5, "%s: chain produce needs epi 1, cnt_init[9], "
+                   "scale_out and no fused norm", who);
+  if (chain == 2 && (!scale_in || !nw))
+    return set_err(5, "%s: chain consume needs scale_in and the norm row",
+                   who);
+  OpBufs b;
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreate(&b.s));
+  int r;
+  const size_t ld = (size_t)N + OPG;  // out row stride per repeat
+  u16 *dx, *dw = nullptr, *dres = nullptr, *dnw = nullptr, *dout16 = nullptr;
+  float* dout32 = nullptr;
+  void *dw8 = nullptr, *dsc = nullptr;
+  if ((r = ob_up16(b, x, (size_t)repeats * K, &dx))) return r;
+  if (kind == 1) {
+    if ((r = ob_upf32(b, w8, (size_t)N * K, &dw8))) return r;
+    if ((r = ob_upf32(b, sc, (size_t)(N / 128) * (K / 128) * 4, &dsc)))
+      return r;
+  } else {
+    if ((r = ob_up16(b, w, (size_t)N * K, &dw))) return r;
+  }
+  if (nw && (r = ob_up16(b, nw, K, &dnw))) return r;
+  if (epi == 2) {
+    if ((r = ob_sent32(b, repeats * ld, &dout32))) return r;
+  } else {
+    if ((r = ob_sent16(b, repeats * ld, &dout16))) return r;
+  }
+  if (res) {
+    // residual rows at the out stride, so alias can copy them in place
+    std::vector<float> h(repeats * ld, CAKE_HIP_OP_SENTINEL);
+    for (int i = 0; i < repeats; ++i)
+      memcpy(h.data() + i * ld, res + (size_t)i * N, sizeof(float) * N);
+    if ((r = ob_up16(b, h.data(), h.size(), &dres))) return r;
+    HIP_TRY(hipStreamSynchronize(b.s));
+    if (alias) dout16 = dres;  // out == res, as the engine does with e->x
+  }
+  void *dws = nullptr, *dcnt = nullptr, *dpart = nullptr, *dsin = nullptr;
+  float* dsout = nullptr;
+  if (kind == 2) {
+    const size_t nc = (size_t)(N + 1) / 2;
+    std::vector<uint32_t> h(nc, cnt_init[0]);
+    if ((r = ob_alloc(b, &dws, (size_t)N * 2 * 4))) return r;
+    if ((r = ob_upf32(b, h.data(), nc * 4, &dcnt))) return r;
+    HIP_TRY(hipStreamSynchronize(b.s));
+  }
+  if (chain == 1) {
+    if ((r = ob_alloc(b, &dpart, (size_t)N * 4))) return r;
+    if ((r = ob_upf32(b, cnt_init, 9 * 4, &dcnt))) return r;
+    if ((r = ob_sent32(b, repeats, &dsout))) return r;
+  }
+  if (chain == 2 && (r = ob_upf32(b, scale_in, 4, &dsin))) return r;
+  for (int i = 0; i < repeats; ++i) {
+    const u16* xi = dx + (size_t)i * K;
+    const u16* ri = dres ? dres + i * ld : nullptr;
+    void* oi = epi == 2 ? (void*)(dout32 + i * ld) : (void*)(dout16 + i * ld);
+    if (kind == 0) {
+      launch_gemv(dw, xi, oi, ri, dnw, eps, N, K, epi, b.s, rows);
+    } else if (kind == 2) {
+      launch_gemv_res_splitk(dw, xi, (u16*)oi, ri, (float*)dws, (u32*)dcnt,
+                             N, K, b.s);
+    } else {
+      NormIO nio{};
+      if (chain == 1) {
+        nio.part = (float*)dpart;
+        nio.cnt = (u32*)dcnt;
+        nio.scale_out = dsout + i;
+        nio.eps = eps;
+      } else if (chain == 2) {
+        nio.scale_in = (const float*)dsin;
+        nio.nw = dnw;
+      }
+      launch_gemv_fp8((const unsigned char*)dw8, (const float*)dsc, xi, oi,
+                      ri, chain == 2 ? nullptr : dnw, eps, N, K, epi, b.s,
+                      nio, rows);
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  if (chain == 1 &&
+      (r = ob_downf32(b, dsout, (size_t)repeats * 4, scale_out)))
+    return r;
+  if (epi == 2) return ob_downf32(b, dout32, repeats * ld * 4, out);
+  return ob_down16(b, dout16, repeats * ld, out);
+}
+
+extern "C" int cake_hip_op_gemv_gateup(int fp8, int I, int K, int rows,
+                                       const float* x, const float* w,
+                                       const uint8_t* w8, const float* sc,
+                                       const float* nw, float eps,
+                                       const float* scale_in, float* out,
+                                       int device) {
+  const char* who = "op_gemv_gateup";
+  if (I < 1) return set_err(5, "%s: I %d < 1", who, I);
+  if (K < 8 || K % 8 != 0 || K > 16384)
+    return set_err(5, "%s: K must be a multiple of 8 in [8,16384] (got %d)",
+                   who, K);
+  if (!x || !out) return set_err(5, "%s: x and out are required", who);
+  if (fp8) {
+    int r = fp8_shape_err(who, I, K);  // I % 128 keeps gate/up blocks apart
+    if (r) return r;
+    if (!w8 || !sc) return set_err(5, "%s: fp8 needs w8 and sc", who);
+    if (rows != 0 && rows != 4)
+      return set_err(5, "%s: the fp8 kernel has 4 rows per block", who);
+    if (scale_in && !nw)
+      return set_err(5, "%s: chain consume needs the norm row", who);
+  } else {
+    if (!w) return set_err(5, "%s: bf16 needs w", who);
+    if (rows != 0 && rows != 4 && rows != 8)
+      return set_err(5, "%s: rows %d not in {0,4,8}", who, rows);
+    if (scale_in) return set_err(5, "%s: the norm chain is fp8 only", who);
+  }
+  OpBufs b;
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreate(&b.s));
+  int r;
+  u16 *dx, *dw = nullptr, *dnw = nullptr, *dout;
+  void *dw8 = nullptr, *dsc = nullptr, *dsin = nullptr;
+  if ((r = ob_up16(b, x, K, &dx))) return r;
+  if (nw && (r = ob_up16(b, nw, K, &dnw))) return r;
+  if ((r = ob_sent16(b, (size_t)I + OPG, &dout))) return r;
+  if (fp8) {
+    if ((r = ob_upf32(b, w8, (size_t)2 * I * K, &dw8))) return r;
+    if ((r = ob_upf32(b, sc, (size_t)(2 * I / 128) * (K / 128) * 4, &dsc)))
+      return r;
+    NormIO nio{};
+    if (scale_in) {
+      if ((r = ob_upf32(b, scale_in, 4, &dsin))) return r;
+      nio.scale_in = (const float*)dsin;
+      nio.nw = dnw;
+    }
+    launch_gemv_gateup_fp8((const unsigned char*)dw8, (const float*)dsc, dx,
+                           dout, scale_in ? nullptr : dnw, eps, I, K, b.s,
+                           nio);
+  } else {
+    if ((r = ob_up16(b, w, (size_t)2 * I * K, &dw))) return r;
+    launch_gemv_gateup(dw, dx, dout, dnw, eps, I, K, rows, b.s);
+  }
+  HIP_TRY(hipGetLastError());
+  return ob_down16(b, dout, (size_t)I + OPG, out);
+}
+
+extern "C" int cake_hip_op_gemv_qkv_rope(int nh, int nkv, int hd, int max_seq,
+                                         int pos, int K, const float* x,
+                                         const float* nw, float eps,
+                                         const float* w, const float* cosv,
+                                         const float* sinv, float* kc,
+                                         float* vc, float* vtc, float* out,
+                                         int device) {
+  const char* who = "op_gemv_qkv_rope";
+  int r = attn_geom_err(who, nh, nkv, hd, max_seq);
+  if (r) return r;
+  if (pos < 0 || pos >= max_seq)
+    return set_err(5, "%s: pos %d outside the cache (max_seq %d)", who, pos,
+                   max_seq);
+  if (K < 8 || K % 8 != 0)
+    return set_err(5, "%s: K must be a positive multiple of 8 (got %d)", who,
+                   K);
+  if (!x || !nw || !w || !out)
+    return set_err(5, "%s: x, nw, w and out are required", who);
+  OpBufs b;
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreate(&b.s));
+  const int Nq = (nh + 2 * nkv) * hd;
+  const size_t ncache = (size_t)nkv * max_seq * hd;
+  const size_t ntab = (size_t)max_seq * (hd / 2);
+  u16 *dx, *dnw, *dw, *dkc, *dvc, *dvtc, *dout;
+  void *dcos, *dsin, *dpos;
+  if ((r = ob_up16(b, x, K, &dx))) return r;
+  if ((r = ob_up16(b, nw, K, &dnw))) return r;
+  if ((r = ob_up16(b, w, (size_t)Nq * K, &dw))) return r;
+  if ((r = ob_up16(b, kc, ncache, &dkc))) return r;
+  if ((r = ob_up16(b, vc, ncache, &dvc))) return r;
+  if ((r = ob_up16(b, vtc, ncache, &dvtc))) return r;
+  if ((r = ob_upf32(b, cosv, ntab * 4, &dcos))) return r;
+  if ((r = ob_upf32(b, sinv, ntab * 4, &dsin))) return r;
+  if ((r = ob_upf32(b, &pos, sizeof(int), &dpos))) return r;
+  // the whole qkv activation row + guards: only the q part may be written
+  if ((r = ob_sent16(b, (size_t)Nq + OPG, &dout))) return r;
+  launch_gemv_qkv_rope(dw, dx, dout, dnw, eps, dkc, dvc, dvtc,
+                       (const float*)dcos, (const float*)dsin,
+                       (const int*)dpos, nh, nkv, hd, max_seq, K, b.s);
+  HIP_TRY(hipGetLastError());
+  if ((r = ob_down16(b, dout, (size_t)Nq + OPG, out))) return r;
+  if ((r = ob_down16(b, dkc, ncache, kc))) return r;
+  if ((r = ob_down16(b, dvc, ncache, vc))) return r;
+  return ob_down16(b, dvtc, ncache, vtc);
+}
+
+extern "C" int cake_hip_op_gemm(int variant, int M, int N, int K, int epi,
+                                int alias, const float* a, const float* w,
+                                const float* res, float* out, int* ran,
+                                int device) {
+  const char* who = "op_gemm";
+  if (variant < GEMM_V128 || variant > GEMM_VLIB)
+    return set_err(5, "%s: variant %d outside [0,4]", who, variant);
+  if (M < 1 || N < 1) return set_err(5, "%s: M %d, N %d", who, M, N);
+  if (K < 8 || K % 8 != 0)
+    return set_err(5, "%s: K must be a positive multiple of 8 (got %d)", who,
+                   K);
+  // the three pipelined big-tile kernels step K in whole 64-wide tiles;
+  // their prologues and tail waits are correct for any tile count >= 1
+  if (variant >= GEMM_V256 && variant <= GEMM_V256P && K % 64 != 0)
+    return set_err(5, "%s: variant %d needs K %% 64 == 0 (got %d)", who,
+                   variant, K);
+  if (epi < 0 || epi > 1) return set_err(5, "%s: epi %d", who, epi);
+  if ((epi == 1) != (res != nullptr))
+    return set_err(5, "%s: res goes with epi 1", who);
+  if (alias && epi != 1)
+    return set_err(5, "%s: alias needs the residual epilogue", who);
+  if (!a || !w || !out || !ran)
+    return set_err(5, "%s: a, w, out and ran are required", who);
+  OpBufs b;
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreate(&b.s));
+  int r;
+  const size_t n = (size_t)M * N;
+  u16 *da, *dw, *dres = nullptr, *dout = nullptr;
+  if ((r = ob_up16(b, a, (size_t)M * K, &da))) return r;
+  if ((r = ob_up16(b, w, (size_t)N * K, &dw))) return r;
+  if (res) {
+    std::vector<float> h(n + OPG, CAKE_HIP_OP_SENTINEL);
+    memcpy(h.data(), res, n * sizeof(float));
+    if ((r = ob_up16(b, h.data(), h.size(), &dres))) return r;
+    HIP_TRY(hipStreamSynchronize(b.s));
+  }
+  if (alias) dout = dres;  // C == res, as the engine's o/down projections
+  else if ((r = ob_sent16(b, n + OPG, &dout))) return r;
+  const bool ok = launch_gemm_variant(da, dw, dout, dres, M, N, K, epi,
+                                      variant, b.s);
+  HIP_TRY(hipGetLastError());
+  *ran = ok ? variant : -1;  // -1: the library rejected the shape
+  return ob_down16(b, dout, n + OPG, out);
+}
+
+extern "C" int cake_hip_op_dequant_fp8(int N, int K, const uint8_t* w8,
+                                       const float* sc, float* out,
+                                       int device) {
+  const char* who = "op_dequant_fp8";
+  int r = fp8_shape_err(who, N, K);
+  if (r) return r;
+  if (!w8 || !sc || !out)
+    return set_err(5, "%s: w8, sc and out are required", who);
+  OpBufs b;
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreate(&b.s));
+  const size_t n = (size_t)N * K;
+  void *dw8, *dsc;
+  u16* dout;
+  if ((r = ob_upf32(b, w8, n, &dw8))) return r;
+  if ((r = ob_upf32(b, sc, (size_t)(N / 128) * (K / 128) * 4, &dsc)))
+    return r;
+  if ((r = ob_sent16(b, n + OPG, &dout))) return r;
+  launch_dequant_fp8((const unsigned char*)dw8, (const float*)dsc, dout, N, K,
+                     b.s);
+  HIP_TRY(hipGetLastError());
+  return ob_down16(b, dout, n + OPG, out);
+}
+
+extern "C" int cake_hip_op_silu_mul_rows(int S, int I, const float* gu,
+                                         float* out, int device) {
+  const char* who = "op_silu_mul_rows";
+  if (S < 1 || I < 8 || I % 8 != 0)
+    return set_err(5, "%s: S %d >= 1 and I %d a positive multiple of 8", who,
+                   S, I);
+  if (!gu || !out) return set_err(5, "%s: gu and out are required", who);
+  OpBufs b;
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreate(&b.s));
+  int r;
+  u16 *dgu, *dout;
+  if ((r = ob_up16(b, gu, (size_t)S * 2 * I, &dgu))) return r;
+  if ((r = ob_sent16(b, (size_t)S * I + OPG, &dout))) return r;
+  launch_silu_mul_rows(dgu, dout, S, I, b.s);
+  HIP_TRY(hipGetLastError());
+  return ob_down16(b, dout, (size_t)S * I + OPG, out);
+}
+
+extern "C" int cake_hip_op_rms_norm_rows(int outer, int inner,
+                                         long outer_stride, int cols,
+                                         float eps, long n, const float* x,
+                                         const float* w, float* out,
+                                         int device) {
+  const char* who = "op_rms_norm_rows";
+  if (outer < 1 || inner < 1 || cols < 1)
+    return set_err(5, "%s: outer %d, inner %d, cols %d", who, outer, inner,
+                   cols);
+  // rows may not overlap, x is read and out written with 16-B vectors
+  if (outer_stride < (long)inner * cols || outer_stride % 8 != 0 ||
+      cols % 8 != 0)
+    return set_err(5, "%s: outer_stride %ld must be a multiple of 8 >= "
+                   "inner * cols, cols %d a multiple of 8", who, outer_stride,
+                   cols);
+  if (n != (long)(outer - 1) * outer_stride + (long)inner * cols)
+    return set_err(5, "%s: buffer of %ld elements, rows end at %ld", who, n,
+                   (long)(outer - 1) * outer_stride + (long)inner * cols);
+  if (!x || !w || !out) return set_err(5, "%s: x, w, out are required", who);
+  OpBufs b;
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreate(&b.s));
+  int r;
+  u16 *dx, *dw, *dout;
+  if ((r = ob_up16(b, x, (size_t)n, &dx))) return r;
+  if ((r = ob_up16(b, w, cols, &dw))) return r;
+  if ((r = ob_sent16(b, (size_t)n + OPG, &dout))) return r;
+  launch_rmsnorm_strided(dx, dw, dout, outer, inner, (size_t)outer_stride,
+                         cols, eps, b.s);
+  HIP_TRY(hipGetLastError());
+  return ob_down16(b, dout, (size_t)n + OPG, out);
+}
+
+// The five linear launches of one decode step of this model, by the very
+// predicates enqueue_layer_decode and enqueue_head_sample use (host only):
+// out[i] = {family, rows, KB} for i = qkv, o, gate-up, down, head.  The
+// opt-in split-K residual GEMV (CAKE_GEMV_SPLITK) is not reflected.
+static void plain_dispatch(int N, int K, bool fp8, int* o) {
+  if (fp8) {
+    o[2] = gemv_fp8_kb(K);
+    o[0] = o[2] ? CAKE_HIP_FAM_GEMV_FP8 : CAKE_HIP_FAM_GEMV_FP8_STREAM;
+    o[1] = gemv_fp8_rows_policy(N);
+  } else {
+    o[2] = gemv_kb(K);
+    o[0] = o[2] ? CAKE_HIP_FAM_GEMV_REG : CAKE_HIP_FAM_GEMV_STREAM;
+    o[1] = gemv_rows_policy(N, K);
+  }
+}
+extern "C" int cake_hip_decode_dispatch(const char* config_json,
+                                        int out[15]) {
+  ModelConfig c;
+  int r = parse_config(config_json, &c);
+  if (r) return r;
+  const int H = c.hidden, I = c.inter;
+  if (fused_qkv_rope_applies(c)) {
+    out[0] = CAKE_HIP_FAM_QKV_ROPE;
+    out[1] = 4;
+    out[2] = gemv_qkv_rope_kb(H);
+  } else {
+    plain_dispatch(c.nqkv(), H, c.fp8, out);
+  }
+  plain_dispatch(H, c.sq(), c.fp8, out + 3);
+  out[6] = c.fp8 ? CAKE_HIP_FAM_GATEUP_FP8 : CAKE_HIP_FAM_GATEUP;
+  out[7] = c.fp8 ? 4 : gemv_gateup_rows_policy();
+  out[8] = c.fp8 ? gemv_fp8_kb(H) : gemv_kb(H);
+  plain_dispatch(H, I, c.fp8, out + 9);
+  plain_dispatch(c.vocab, H, false, out + 12);  // lm_head stays bf16
+  return 0;
+}
+
+// The kernel choices the product makes for a linear layer (host only).
+// kind: 0 plain GEMV, 1 gate-up GEMV, 2 fused qkv-rope GEMV, 3 split-K
+// residual GEMV, 4 prefill GEMM.  out = {family, rows, KB (0 = streaming
+// kernel), library first, hand-written GEMM variant}.
+extern "C" int cake_hip_linear_dispatch(int kind, int n, int K, int M,
+                                        int fp8, int out[5]) {
+  if (kind < 0 || kind > 4 || n < 1 || K < 1 || M < 1)
+    return set_err(5, "linear_dispatch: kind %d, n %d, K %d, M %d", kind, n,
+                   K, M);
+  if (fp8 && kind >= 2)
+    return set_err(5, "linear_dispatch: kind %d has no fp8 kernel", kind);
+  out[0] = out[1] = out[2] = out[3] = out[4] = 0;
+  switch (kind) {
+    case 0:
+      plain_dispatch(n, K, fp8 != 0, out);
+      break;
+    case 1:
+      if (K > 16384)
+        return set_err(5, "linear_dispatch: gate-up needs K <= 16384");
+      out[0] = fp8 ? CAKE_HIP_FAM_GATEUP_FP8 : CAKE_HIP_FAM_GATEUP;
+      out[1] = fp8 ? 4 : gemv_gateup_rows_policy();
+      out[2] = fp8 ? gemv_fp8_kb(K) : gemv_kb(K);
+      break;
+    case 2:
+      out[0] = CAKE_HIP_FAM_QKV_ROPE;
+      out[1] = 4;
+      out[2] = gemv_qkv_rope_kb(K);
+      break;
+    case 3:
+      out[0] = CAKE_HIP_FAM_SPLITK;
+      out[1] = 2;
+      out[2] = gemv_splitk_kb(K);
+      break;
+    default: {
+      const GemmPolicy p = gemm_policy(M, n, K);
+      out[0] = CAKE_HIP_FAM_GEMM;
+      out[3] = p.lib_first ? 1 : 0;
+      out[4] = p.variant;
+    }
+  }
   return 0;
 }
 

@@ -21,9 +21,21 @@ void launch_silu_mul(const u16* g, const u16* u, u16* out, size_t n,
                      hipStream_t s);
 void launch_silu_mul_rows(const u16* gu, u16* out, int S, int I,
                           hipStream_t s);
+// rows_override: output rows per block (1|2|4|8), 0 = gemv_rows_policy
 void launch_gemv(const u16* W, const u16* x, void* out, const u16* res,
                  const u16* nw, float eps, int N, int K, int epi,
-                 hipStream_t s);
+                 hipStream_t s, int rows_override = 0);
+// host-side kernel choices of the GEMV launchers: rows per block, and the
+// template KB (2048-wide k blocks for bf16, 4096-wide for fp8; 0 = the
+// streaming kernel)
+int gemv_rows_policy(int N, int K);
+int gemv_fp8_rows_policy(int N);
+int gemv_gateup_rows_policy();  // bf16 gate-up: 4, or CAKE_GU_ROWS = 8
+int gemv_kb(int K);
+int gemv_fp8_kb(int K);
+int gemv_qkv_rope_kb(int K);
+int gemv_splitk_kb(int K);
+// rows: channels per block, 8 or (anything else, 0 included) 4
 void launch_gemv_gateup(const u16* W, const u16* x, u16* out, const u16* nw,
                         float eps, int I, int K, int rows, hipStream_t s);
 void launch_gemv_res_splitk(const u16* W, const u16* x, u16* out,
@@ -53,7 +65,7 @@ struct NormIO {
 void launch_gemv_fp8(const unsigned char* W, const float* sc, const u16* x,
                      void* out, const u16* res, const u16* nw, float eps,
                      int N, int K, int epi, hipStream_t s,
-                     NormIO nio = NormIO{});
+                     NormIO nio = NormIO{}, int rows_override = 0);
 void launch_gemv_gateup_fp8(const unsigned char* W, const float* sc,
                             const u16* x, u16* out, const u16* nw, float eps,
                             int I, int K, hipStream_t s,
@@ -139,6 +151,25 @@ void launch_sample(const float* logits, int V, const SampleWs& b, u32* tok,
                    float inv_temp, int top_k, float top_p, float penalty,
                    int last_n, int advance_hist, uint64_t seed,
                    hipStream_t s);
+// Prefill GEMM variants: the four hand-written kernels and hipBLASLt.
+enum {
+  GEMM_V128 = 0,      // k_gemm_bf16, 128^2 tile, any K % 8 == 0
+  GEMM_V256 = 1,      // k_gemm_256, K % 64 == 0
+  GEMM_V128X256 = 2,  // k_gemm_128x256, K % 64 == 0
+  GEMM_V256P = 3,     // k_gemm_256p, K % 64 == 0
+  GEMM_VLIB = 4,      // hipBLASLt (may reject a shape)
+};
+struct GemmPolicy {
+  bool lib_first;  // try hipBLASLt, fall back to `variant` if it rejects
+  int variant;     // the hand-written kernel for this shape
+};
+// the choice the product makes for this shape (env knobs + size policy)
+GemmPolicy gemm_policy(int M, int N, int K);
+// runs exactly `variant`; false only when GEMM_VLIB rejects the shape
+bool launch_gemm_variant(const u16* A, const u16* W, u16* C, const u16* res,
+                         int M, int N, int K, int epi, int variant,
+                         hipStream_t s);
+// launch_gemm == gemm_policy -> [library ->] launch_gemm_variant
 void launch_gemm(const u16* A, const u16* W, u16* C, const u16* res, int M,
                  int N, int K, int epi, hipStream_t s);
 // hipBLASLt path for the plain prefill GEMMs (gemm_lib.hip); false => caller

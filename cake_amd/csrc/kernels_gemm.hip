@@ -576,8 +576,7 @@ __global__ __launch_bounds__(512) void k_gemm_256p(
   }
 }
 
-void launch_gemm(const u16* A, const u16* W, u16* C, const u16* res, int M,
-                 int N, int K, int epi, hipStream_t s) {
+GemmPolicy gemm_policy(int M, int N, int K) {
   // hipBLASLt first for these plain GEMMs (CAKE_GEMM_LIB=0 restores the
   // hand-written kernels; they also remain the fallback for any shape the
   // library heuristic rejects)
@@ -594,11 +593,11 @@ void launch_gemm(const u16* A, const u16* W, u16* C, const u16* res, int M,
   const long g128x256 = (long)((M + 127) / 128) * ((N + 255) / 256);
   const bool ours_wins =
       K <= 4096 && M >= 1024 && g128x256 >= 200 && g128x256 <= 256;
-  if (use_lib && !ours_wins &&
-      launch_gemm_lib(A, W, C, res, M, N, K, epi, s))
-    return;
+  GemmPolicy p;
+  p.lib_first = use_lib && !ours_wins;
   // variant select: 0 = 128^2 baseline, 1 = 256^2 counted-vmcnt,
-  // 2 = 128x256 3-buffer two-tile lookahead (CAKE_GEMM_VAR overrides)
+  // 2 = 128x256 3-buffer two-tile lookahead, 3 = 256^2 fine-phase
+  // (CAKE_GEMM_VAR overrides)
   static const int var = [] {
     const char* v = getenv("CAKE_GEMM_VAR");
     if (v) return atoi(v);
@@ -617,7 +616,24 @@ void launch_gemm(const u16* A, const u16* W, u16* C, const u16* res, int M,
       (long)mt128 * nt256 >= 200 && K % 64 == 0 &&
       !(getenv("CAKE_GEMM_MIXED") && atoi(getenv("CAKE_GEMM_MIXED")) == 0);
   if ((var == 2 || mixed_128x256) && (long)mt128 * nt256 >= 200 &&
-      K % 64 == 0) {
+      K % 64 == 0)
+    p.variant = GEMM_V128X256;
+  else if (var == 3 && (long)mt256 * nt256 >= 200 && K % 64 == 0)
+    p.variant = GEMM_V256P;
+  else if (var >= 1 && (long)mt256 * nt256 >= 200 && K % 64 == 0)
+    p.variant = GEMM_V256;
+  else
+    p.variant = GEMM_V128;
+  return p;
+}
+
+bool launch_gemm_variant(const u16* A, const u16* W, u16* C, const u16* res,
+                         int M, int N, int K, int epi, int variant,
+                         hipStream_t s) {
+  if (variant == GEMM_VLIB)
+    return launch_gemm_lib(A, W, C, res, M, N, K, epi, s);
+  const int mt128 = (M + 127) / 128, nt256 = (N + 255) / 256;
+  if (variant == GEMM_V128X256) {
     static bool attr2 = false;
     if (!attr2) {
       hipFuncSetAttribute((const void*)&k_gemm_128x256<0>,
@@ -633,10 +649,10 @@ void launch_gemm(const u16* A, const u16* W, u16* C, const u16* res, int M,
     else
       hipLaunchKernelGGL(k_gemm_128x256<1>, grid, dim3(512), 147456, s, A, W,
                          C, res, M, N, K);
-    return;
+    return true;
   }
   const int mt = (M + 255) / 256, nt = (N + 255) / 256;
-  if (var == 3 && (long)mt * nt >= 200 && K % 64 == 0) {
+  if (variant == GEMM_V256P) {
     static bool attr3 = false;
     if (!attr3) {
       hipFuncSetAttribute((const void*)&k_gemm_256p<0>,
@@ -652,9 +668,9 @@ void launch_gemm(const u16* A, const u16* W, u16* C, const u16* res, int M,
     else
       hipLaunchKernelGGL(k_gemm_256p<1>, grid, dim3(512), 131072, s, A, W, C,
                          res, M, N, K);
-    return;
+    return true;
   }
-  if (var >= 1 && (long)mt * nt >= 200 && K % 64 == 0) {
+  if (variant == GEMM_V256) {
     static bool attr_set = false;
     if (!attr_set) {
       hipFuncSetAttribute((const void*)&k_gemm_256<0>,
@@ -670,7 +686,7 @@ void launch_gemm(const u16* A, const u16* W, u16* C, const u16* res, int M,
     else
       hipLaunchKernelGGL(k_gemm_256<1>, grid, dim3(512), 131072, s, A, W, C,
                          res, M, N, K);
-    return;
+    return true;
   }
   dim3 grid((M + GEMM_BM - 1) / GEMM_BM, (N + GEMM_BN - 1) / GEMM_BN);
   size_t lds = 2 * (size_t)(GEMM_BM + GEMM_BN) * GEMM_BK * 2;
@@ -680,4 +696,14 @@ void launch_gemm(const u16* A, const u16* W, u16* C, const u16* res, int M,
   else
     hipLaunchKernelGGL(k_gemm_bf16<1>, grid, dim3(256), lds, s, A, W, C, res,
                        M, N, K);
+  return true;
+}
+
+void launch_gemm(const u16* A, const u16* W, u16* C, const u16* res, int M,
+                 int N, int K, int epi, hipStream_t s) {
+  const GemmPolicy p = gemm_policy(M, N, K);
+  if (p.lib_first && launch_gemm_variant(A, W, C, res, M, N, K, epi,
+                                         GEMM_VLIB, s))
+    return;
+  launch_gemm_variant(A, W, C, res, M, N, K, epi, p.variant, s);
 }

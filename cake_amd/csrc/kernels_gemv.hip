@@ -429,6 +429,50 @@ __global__ __launch_bounds__(256) void k_gemv_qkv_rope(
   }
 }
 
+// ---- host-side kernel choices (queried by cake_hip_linear_dispatch; the
+// launchers below go through the same functions) ---------------------------
+int gemv_kb(int K) {  // k_gemv_reg / k_gemv_gateup; 0 = k_gemv_stream
+  if (K > 16384) return 0;
+  return K <= 4096 ? 2 : K <= 8192 ? 4 : 8;
+}
+int gemv_fp8_kb(int K) {  // k_gemv_fp8 / k_gemv_gateup_fp8; 0 = stream
+  if (K > 16384) return 0;
+  return K <= 4096 ? 1 : K <= 8192 ? 2 : 4;
+}
+int gemv_qkv_rope_kb(int K) {
+  return K <= 2048 ? 1 : K <= 4096 ? 2 : K <= 8192 ? 4 : 8;
+}
+int gemv_splitk_kb(int K) {  // KB of the half-K slice
+  const int kpart = K / 2;
+  return kpart <= 2048 ? 1 : kpart <= 4096 ? 2 : kpart <= 8192 ? 4 : 8;
+}
+int gemv_rows_policy(int N, int K) {
+  // small row-count per block keeps the grid >= ~2048 workgroups on the
+  // usual decode shapes (256 CUs need many blocks to reach HBM peak)
+  static const int env_small = [] {
+    const char* v = getenv("CAKE_GEMV_ROWS_SMALL");
+    return v ? atoi(v) : 0;
+  }();
+  if (N >= 16384) return 8;                 // lm_head: maximal block count
+  if (env_small) return env_small;          // A/B override
+  if (K >= 8192) return 4;                  // long rows amortize x reload
+  return (N >= 6144) ? 4 : 2;
+}
+int gemv_gateup_rows_policy() {
+  static const int rows = [] {
+    const char* v = getenv("CAKE_GU_ROWS");
+    return v && atoi(v) == 8 ? 8 : 4;
+  }();
+  return rows;
+}
+int gemv_fp8_rows_policy(int N) {
+  static const int env_rows = [] {
+    const char* v = getenv("CAKE_FP8_ROWS");
+    return v ? atoi(v) : 0;
+  }();
+  return N >= 16384 ? 8 : (env_rows ? env_rows : 4);
+}
+
 void launch_gemv_qkv_rope(const u16* W, const u16* x, u16* out, const u16* nw,
                           float eps, u16* kc, u16* vc, u16* vtc,
                           const float* cost, const float* sint,
@@ -440,9 +484,10 @@ void launch_gemv_qkv_rope(const u16* W, const u16* x, u16* out, const u16* nw,
   hipLaunchKernelGGL((k_gemv_qkv_rope<KB>), grid, dim3(256), 0, s, W, x,    \
                      out, nw, eps, kc, vc, vtc, cost, sint, pos, nh, nkv,   \
                      hd, max_seq, K)
-  if (K <= 2048) QKR(1);
-  else if (K <= 4096) QKR(2);
-  else if (K <= 8192) QKR(4);
+  const int kb = gemv_qkv_rope_kb(K);
+  if (kb == 1) QKR(1);
+  else if (kb == 2) QKR(2);
+  else if (kb == 4) QKR(4);
   else QKR(8);
 #undef QKR
 }
@@ -613,12 +658,23 @@ __device__ inline void normchain_produce(const NormIO& nio, float vsq,
   }
   v = __shfl(v, 0, WAVE);
   if (v % shard_total != shard_total - 1) return;
+  // The elected arrival is the LAST of its class in this launch (launches
+  // on these counters are stream-ordered), so it re-zeroes the word: a
+  // monotonic u32 under a modulus that does not divide 2^32 (shard_total
+  // is e.g. 160) shifts its election phase when it wraps, after ~4e5
+  // tokens, and the scale would then come from a half-arrived launch.
   u32 tv = 0;
-  if (lane == 0)
+  if (lane == 0) {
+    __hip_atomic_store(&nio.cnt[shard], 0u, __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
     tv = __hip_atomic_fetch_add(&nio.cnt[8], 1u, __ATOMIC_RELAXED,
                                 __HIP_MEMORY_SCOPE_AGENT);
+  }
   tv = __shfl(tv, 0, WAVE);
   if (tv % 8u != 7u) return;
+  if (lane == 0)  // modulus 8 survives the wrap; zeroed for symmetry
+    __hip_atomic_store(&nio.cnt[8], 0u, __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
   // Elected reduce: ONE agent acquire then PLAIN unguarded clamped loads
   // in batches of 8 (relaxed-ATOMIC loads do not batch — each emits its
   // own wait, ~20 serial uncached round trips on the elected
@@ -1171,14 +1227,14 @@ void launch_gemv_res_splitk(const u16* W, const u16* x, u16* out,
                             const u16* res, float* ws, u32* cnt, int N,
                             int K, hipStream_t s) {
   // K/2 per slice; pick KB for the half-K
-  const int kpart = K / 2;
+  const int kb = gemv_splitk_kb(K);
   dim3 grid((N + 1) / 2, 2);
 #define SPK(KB)                                                             \
   hipLaunchKernelGGL((k_gemv_splitk_res<2, KB, 2>), grid, dim3(256), 0, s,  \
                      W, x, out, res, ws, cnt, N, K)
-  if (kpart <= 2048) SPK(1);
-  else if (kpart <= 4096) SPK(2);
-  else if (kpart <= 8192) SPK(4);
+  if (kb == 1) SPK(1);
+  else if (kb == 2) SPK(2);
+  else if (kb == 4) SPK(4);
   else SPK(8);
 #undef SPK
 }
@@ -1188,7 +1244,8 @@ static void gemv_dispatch_kb(const u16* W, const u16* x, void* out,
                              const u16* res, const u16* nw, float eps, int N,
                              int K, hipStream_t s) {
   dim3 grid((N + ROWS - 1) / ROWS);
-  if (K > 16384) {
+  const int kb = gemv_kb(K);
+  if (kb == 0) {
     hipLaunchKernelGGL((k_gemv_stream<ROWS, EPI>), grid, dim3(256), 0, s, W,
                        x, out, res, N, K);
     return;
@@ -1202,26 +1259,16 @@ static void gemv_dispatch_kb(const u16* W, const u16* x, void* out,
       hipLaunchKernelGGL((k_gemv_reg<ROWS, EPI, false, KB>), grid,         \
                          dim3(256), 0, s, W, x, out, res, nw, eps, N, K);  \
   } while (0)
-  if (K <= 4096) GEMV_KB(2);
-  else if (K <= 8192) GEMV_KB(4);
+  if (kb == 2) GEMV_KB(2);
+  else if (kb == 4) GEMV_KB(4);
   else GEMV_KB(8);
 #undef GEMV_KB
 }
 
 void launch_gemv(const u16* W, const u16* x, void* out, const u16* res,
                  const u16* nw, float eps, int N, int K, int epi,
-                 hipStream_t s) {
-  // small row-count per block keeps the grid >= ~2048 workgroups on the
-  // usual decode shapes (256 CUs need many blocks to reach HBM peak)
-  static const int env_small = [] {
-    const char* v = getenv("CAKE_GEMV_ROWS_SMALL");
-    return v ? atoi(v) : 0;
-  }();
-  int rows;
-  if (N >= 16384) rows = 8;                 // lm_head: maximal block count
-  else if (env_small) rows = env_small;     // A/B override
-  else if (K >= 8192) rows = 4;             // long rows amortize x reload
-  else rows = (N >= 6144) ? 4 : 2;
+                 hipStream_t s, int rows_override) {
+  const int rows = rows_override ? rows_override : gemv_rows_policy(N, K);
 #define GEMV_R(R, EPI) gemv_dispatch_kb<R, EPI>(W, x, out, res, nw, eps, N, K, s)
 #define GEMV_EPI(EPI)                          \
   do {                                         \
@@ -1239,6 +1286,7 @@ void launch_gemv(const u16* W, const u16* x, void* out, const u16* res,
 void launch_gemv_gateup(const u16* W, const u16* x, u16* out, const u16* nw,
                         float eps, int I, int K, int rows, hipStream_t s) {
   if (K > 16384) return;  // guarded at engine create (K = hidden <= 16384)
+  const int kb = gemv_kb(K);
 #define GU_KB2(ROWS, KB)                                                    \
   do {                                                                      \
     dim3 grid((I + ROWS - 1) / ROWS);                                       \
@@ -1254,21 +1302,19 @@ void launch_gemv_gateup(const u16* W, const u16* x, u16* out, const u16* nw,
     if (rows >= 8) GU_KB2(8, KB);                                           \
     else GU_KB2(4, KB);                                                     \
   } while (0)
-  if (K <= 4096) GU_KB(2);
-  else if (K <= 8192) GU_KB(4);
+  if (kb == 2) GU_KB(2);
+  else if (kb == 4) GU_KB(4);
   else GU_KB(8);
 #undef GU_KB
 #undef GU_KB2
 }
 void launch_gemv_fp8(const unsigned char* W, const float* sc, const u16* x,
                      void* out, const u16* res, const u16* nw, float eps,
-                     int N, int K, int epi, hipStream_t s, NormIO nio) {
+                     int N, int K, int epi, hipStream_t s, NormIO nio,
+                     int rows_override) {
   const int nkb = (K + 127) / 128;
-  static const int env_rows = [] {
-    const char* v = getenv("CAKE_FP8_ROWS");
-    return v ? atoi(v) : 0;
-  }();
-  const int rows = N >= 16384 ? 8 : (env_rows ? env_rows : 4);
+  const int rows = rows_override ? rows_override : gemv_fp8_rows_policy(N);
+  const int kb = gemv_fp8_kb(K);
 #define F8_KB(R, EPI, KB)                                                   \
   do {                                                                      \
     dim3 grid((N + R - 1) / R);                                             \
@@ -1283,12 +1329,12 @@ void launch_gemv_fp8(const unsigned char* W, const float* sc, const u16* x,
   } while (0)
 #define F8_R(R, EPI)                                                        \
   do {                                                                      \
-    if (K > 16384) {                                                        \
+    if (kb == 0) {                                                          \
       dim3 grid((N + R - 1) / R);                                           \
       hipLaunchKernelGGL((k_gemv_fp8_stream<R, EPI>), grid, dim3(256), 0,   \
                          s, W, sc, x, out, res, N, K, nkb, nio);            \
-    } else if (K <= 4096) F8_KB(R, EPI, 1);                                 \
-    else if (K <= 8192) F8_KB(R, EPI, 2);                                   \
+    } else if (kb == 1) F8_KB(R, EPI, 1);                                   \
+    else if (kb == 2) F8_KB(R, EPI, 2);                                     \
     else F8_KB(R, EPI, 4);                                                  \
   } while (0)
   if (epi == 0) { if (rows == 8) F8_R(8, 0); else F8_R(4, 0); }
@@ -1301,6 +1347,7 @@ void launch_gemv_gateup_fp8(const unsigned char* W, const float* sc,
                             const u16* x, u16* out, const u16* nw, float eps,
                             int I, int K, hipStream_t s, NormIO nio) {
   const int nkb = (K + 127) / 128;
+  const int kb = gemv_fp8_kb(K);  // K = hidden <= 16384 (engine create)
   dim3 grid((I + 3) / 4);
 #define GU8_KB(KB)                                                          \
   do {                                                                      \
@@ -1312,8 +1359,8 @@ void launch_gemv_gateup_fp8(const unsigned char* W, const float* sc,
                          dim3(256), 0, s, W, sc, x, out, nw, eps, I, K,     \
                          nkb, nio);                                         \
   } while (0)
-  if (K <= 4096) GU8_KB(1);
-  else if (K <= 8192) GU8_KB(2);
+  if (kb == 1) GU8_KB(1);
+  else if (kb == 2) GU8_KB(2);
   else GU8_KB(4);
 #undef GU8_KB
 }

@@ -189,6 +189,104 @@ int cake_hip_op_attn_decode(int nh, int nkv, int hd, int max_seq, int pos,
  * split_min_s, decode grid_y (0 = per-head kernel)}. */
 int cake_hip_attn_dispatch(int S, int nh, int nkv, int hd, int out[6]);
 
+/* Linear-layer op entries (test-only): GEMV, fp8 GEMV, gate-up, fused
+ * qkv-rope, prefill GEMM, fp8 dequant.  Conventions of the attention entries
+ * (private buffers of exact size, private stream, arguments validated before
+ * any device call: error 5).  Every OUTPUT buffer has CAKE_HIP_OP_GUARD
+ * elements past its end and starts filled with CAKE_HIP_OP_SENTINEL; the
+ * guards are returned behind the payload, so a store past the end or an
+ * element that no block wrote shows.  bf16 tensors cross as f32. */
+#define CAKE_HIP_OP_GUARD 16
+#define CAKE_HIP_OP_SENTINEL (-1152921504606846976.0f) /* -2^60 */
+/* kind 0: launch_gemv (bf16 w (N,K)); 1: launch_gemv_fp8 (w8 (N,K) e4m3fn
+ * bytes + sc (N/128, K/128) f32; N % 128 == 0, K % 128 == 0); 2: the
+ * split-K residual GEMV (bf16, K % 16 == 0, epi 1 only).  K % 8 == 0, K >= 8.
+ * epi 0: bf16 out; 1: bf16 out + res; 2: f32 out.  nw != NULL fuses the
+ * rms_norm with eps (K <= 16384).  rows: output rows per block, 0 = the
+ * product's policy (bf16 1|2|4|8, fp8 4|8).  alias: out == res, as the
+ * engine's o/down projections run.  The kernel is launched `repeats` (1..16)
+ * times back to back, repeat i on x row i and res row i; out is
+ * (repeats, N + CAKE_HIP_OP_GUARD).
+ * Counters are set once, before the first launch: split-K sets every arrival
+ * word to cnt_init[0]; chain 1 (fp8 norm-chain produce, epi 1) sets the nine
+ * words to cnt_init[0..9) and returns scale_out[repeats]; chain 2 (consume)
+ * normalizes x with *scale_in and the nw row instead of the fused norm. */
+int cake_hip_op_gemv(int kind, int N, int K, int epi, int rows, int alias,
+                     int repeats, const float *x, const float *w,
+                     const uint8_t *w8, const float *sc, const float *res,
+                     const float *nw, float eps, int chain,
+                     const uint32_t *cnt_init, const float *scale_in,
+                     float *scale_out, float *out, int device);
+/* out[c] = silu(g_c) * u_c, g = W[c,:].xn, u = W[I+c,:].xn; w is (2I, K).
+ * bf16: rows 0|4|8.  fp8: I % 128 == 0, K % 128 == 0, sc (2I/128, K/128);
+ * scale_in != NULL is the norm-chain consume (needs nw).  K <= 16384.
+ * out is (I + CAKE_HIP_OP_GUARD). */
+int cake_hip_op_gemv_gateup(int fp8, int I, int K, int rows, const float *x,
+                            const float *w, const uint8_t *w8,
+                            const float *sc, const float *nw, float eps,
+                            const float *scale_in, float *out, int device);
+/* Fused rms_norm -> qkv GEMV -> rope -> KV store of one decode row at `pos`.
+ * w ((nh+2*nkv)*hd, K); cos/sin (max_seq, hd/2) f32; kc/vc/vtc IN/OUT images
+ * as in op_kv_store; out ((nh+2*nkv)*hd + CAKE_HIP_OP_GUARD) is the qkv
+ * activation row: the roped q rows, then sentinels (k and v go to the cache
+ * only). */
+int cake_hip_op_gemv_qkv_rope(int nh, int nkv, int hd, int max_seq, int pos,
+                              int K, const float *x, const float *nw,
+                              float eps, const float *w, const float *cosv,
+                              const float *sinv, float *kc, float *vc,
+                              float *vtc, float *out, int device);
+/* C[M,N] = A[M,K] @ W[N,K]^T (+ res) by an explicit variant: 0 128^2 tile,
+ * 1 256^2, 2 128x256, 3 256^2 fine-phase, 4 hipBLASLt.  Variants 1..3 need
+ * K % 64 == 0 (any number of 64-wide tiles >= 1); 0 and 4 take K % 8 == 0.
+ * alias: C == res.  *ran = the variant that ran, or -1 when the library
+ * rejected the shape (out then holds sentinels, or res when aliased).  out is
+ * (M*N + CAKE_HIP_OP_GUARD). */
+int cake_hip_op_gemm(int variant, int M, int N, int K, int epi, int alias,
+                     const float *a, const float *w, const float *res,
+                     float *out, int *ran, int device);
+/* Blockwise fp8 -> bf16 dequant (N % 128 == 0, K % 128 == 0); out is
+ * (N*K + CAKE_HIP_OP_GUARD). */
+int cake_hip_op_dequant_fp8(int N, int K, const uint8_t *w8, const float *sc,
+                            float *out, int device);
+/* Prefill silu_mul over S rows of gu (S, 2I) = [gate | up]: out[s, c] =
+ * silu(gu[s, c]) * gu[s, I + c]; I % 8 == 0.  out is
+ * (S*I + CAKE_HIP_OP_GUARD). */
+int cake_hip_op_silu_mul_rows(int S, int I, const float *gu, float *out,
+                              int device);
+/* rms_norm of outer*inner rows of `cols` elements inside one buffer of n
+ * elements: row r starts at (r / inner) * outer_stride + (r % inner) * cols
+ * (the per-head QK-norm layout; inner = rows, outer = 1 is the plain form).
+ * cols % 8 == 0, outer_stride % 8 == 0, outer_stride >= inner * cols,
+ * n == (outer-1) * outer_stride + inner * cols.  out is
+ * (n + CAKE_HIP_OP_GUARD) in the same layout; elements between the rows keep
+ * the sentinel. */
+int cake_hip_op_rms_norm_rows(int outer, int inner, long outer_stride,
+                              int cols, float eps, long n, const float *x,
+                              const float *w, float *out, int device);
+/* Host only: the kernel the product launches for a linear layer.  kind 0
+ * plain GEMV (n = N), 1 gate-up GEMV (n = I), 2 fused qkv-rope GEMV, 3
+ * split-K residual GEMV, 4 prefill GEMM (M rows).  out = {family
+ * (CAKE_HIP_FAM_*), rows per block, KB (k blocks held in registers; 0 = the
+ * streaming kernel), GEMM: library first (0|1), GEMM: hand-written variant}. */
+enum {
+  CAKE_HIP_FAM_GEMV_REG = 0,
+  CAKE_HIP_FAM_GEMV_STREAM = 1,
+  CAKE_HIP_FAM_GEMV_FP8 = 2,
+  CAKE_HIP_FAM_GEMV_FP8_STREAM = 3,
+  CAKE_HIP_FAM_GATEUP = 4,
+  CAKE_HIP_FAM_GATEUP_FP8 = 5,
+  CAKE_HIP_FAM_QKV_ROPE = 6,
+  CAKE_HIP_FAM_SPLITK = 7,
+  CAKE_HIP_FAM_GEMM = 8,
+};
+int cake_hip_linear_dispatch(int kind, int n, int K, int M, int fp8,
+                             int out[5]);
+/* Host only: the five linear launches of one decode step of the model in
+ * config_json, chosen by the predicates the engine itself uses: out[3*i..] =
+ * {family, rows, KB} for i = qkv, o, gate-up, down, head.  The opt-in
+ * split-K residual GEMV is not reflected. */
+int cake_hip_decode_dispatch(const char *config_json, int out[15]);
+
 /* ---- observability (bench roofline evidence) ----------------------------
  * JSON {"kernels": {name: {"launches": n, "ms": t, "bytes": b}}} — per-
  * kernel-family hipEvent timing + algorithmic bytes, collected while

@@ -101,12 +101,16 @@ def test_op_gemv_small_k():
     (200, 260, 128),       # M and N tails
     (2048, 1536, 4096),    # prefill-like shape
     (33, 128256 // 16, 64),  # wide-N-ish
-    (2048, 28672, 4096),   # gate_up prefill shape (256^2 counted-vmcnt path)
-    (300, 51300, 256),     # 256^2 path with M and N tails
-    (256, 384, 96),        # ragged K (% 64 != 0): masked tail tile
-    (200, 300, 40),        # ragged K smaller than one 64-wide tile
+    (2048, 28672, 4096),   # gate_up prefill shape (hand-written: 256^2)
+    (300, 51300, 256),     # hand-written: 256^2 with M and N tails
+    (256, 384, 96),        # ragged K (% 64 != 0): masked tail tile (128^2)
+    (200, 300, 40),        # ragged K smaller than one 64-wide tile (128^2)
 ])
 def test_op_gemm(M, N, K):
+    """The product dispatch (op_linear: hipBLASLt first for all of these
+    shapes) AND the hand-written kernel the policy keeps behind the library
+    for the shape, forced through the explicit-variant entry.  Sharper
+    per-variant checks live in test_linear_ops_gpu.py."""
     # asymmetric random operands (transpose-detecting — guide §5.4 rule 16)
     rng = np.random.default_rng(M * 7 + N)
     x = rng.standard_normal((M, K)).astype(np.float32) * 0.5
@@ -115,6 +119,11 @@ def test_op_gemm(M, N, K):
     ref = quantize_bf16(x) @ quantize_bf16(w).T
     # bf16 inputs, f32 accumulate: error grows ~sqrt(K) * 2^-8
     assert rel_err(got, ref) < 2e-2
+    variant = cake_amd.linear_dispatch("gemm", N, K, M=M)["variant"]
+    ours, guards, ran = cake_amd.op_gemm(x, w, variant)
+    assert ran == variant
+    assert (guards == cake_amd.OP_SENTINEL).all()
+    assert rel_err(ours, ref) < 2e-2
 
 
 # ---------------------------------------------------------------------------
