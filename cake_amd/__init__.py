@@ -66,6 +66,9 @@ def _load_lib():
     lib.cake_hip_op_attn_prefill.argtypes = [c] * 11 + [fp] * 5 + [c]
     lib.cake_hip_op_attn_decode.argtypes = [c] * 8 + [fp] * 4 + [c]
     lib.cake_hip_attn_dispatch.argtypes = [c, c, c, c, ctypes.POINTER(c)]
+    lib.cake_hip_attn_decode_path.argtypes = [c, c, c, c]
+    lib.cake_hip_op_attn_decode_seq.argtypes = [c] * 7 + \
+        [ctypes.POINTER(c)] + [fp] * 4 + [u32p, c]
     u8p = ctypes.POINTER(ctypes.c_uint8)
     lib.cake_hip_op_gemv.argtypes = [c] * 7 + [fp, fp, u8p, fp, fp, fp, f, c,
                                                u32p, fp, fp, fp, c]
@@ -286,6 +289,35 @@ def attn_dispatch(S, nh, nkv, hd):
     _check(_lib.cake_hip_attn_dispatch(S, nh, nkv, hd, o))
     return dict(pfv=o[0], nw=o[1], split=o[2], deep=o[3], split_min_s=o[4],
                 decode_grid_y=o[5])
+
+
+def attn_decode_path(nh, nkv, hd, nchunk):
+    """The decode-attention kernel the product launches for this geometry and
+    chunk count (host only): 0 per-head, 1 grouped, 2 short-context (the
+    default at nchunk 4).  The library reads CAKE_ATTN_SHORT on every call:
+    0 = never the short kernel, 2 = also at nchunk 8."""
+    return _lib.cake_hip_attn_decode_path(nh, nkv, hd, nchunk)
+
+
+def op_attn_decode_seq(q, kc, vc, pos, nchunks, window=0, device=0):
+    """op_attn_decode with a chunk count per launch, all launches back to
+    back on one set of buffers.  Returns (out (len(nchunks), nh*hd), arrival
+    counters (nh,) after the last launch; they start at 0)."""
+    q = np.ascontiguousarray(q, dtype=np.float32)
+    nh, hd = q.shape
+    kc = np.ascontiguousarray(kc, dtype=np.float32)
+    nkv, max_seq = kc.shape[0], kc.shape[1]
+    _, qp = _f32_shaped(q, (nh, hd), "q")
+    _, kp = _f32_shaped(kc, (nkv, max_seq, hd), "kc")
+    _v, vp = _f32_shaped(vc, (nkv, max_seq, hd), "vc")
+    nc = (ctypes.c_int * len(nchunks))(*[int(x) for x in nchunks])
+    out = np.empty((len(nchunks), nh * hd), dtype=np.float32)
+    cnt = np.empty(nh, dtype=np.uint32)
+    _check(_lib.cake_hip_op_attn_decode_seq(
+        nh, nkv, hd, max_seq, pos, window, len(nchunks), nc, qp, kp, vp,
+        out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+        cnt.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), device))
+    return out, cnt
 
 
 # ---- linear-layer op entries (GEMV / fp8 / GEMM) --------------------------

@@ -2043,6 +2043,55 @@ extern "C" int cake_hip_attn_dispatch(int S, int nh, int nkv, int hd,
   return 0;
 }
 
+extern "C" int cake_hip_attn_decode_path(int nh, int nkv, int hd, int nchunk) {
+  return attn_decode_path(nh, nkv, hd, nchunk);
+}
+
+extern "C" int cake_hip_op_attn_decode_seq(
+    int nh, int nkv, int hd, int max_seq, int pos, int window, int nlaunch,
+    const int* nchunks, const float* q, const float* kc, const float* vc,
+    float* out, uint32_t* cnt_out, int device) {
+  const char* who = "op_attn_decode_seq";
+  int r = attn_geom_err(who, nh, nkv, hd, max_seq);
+  if (r) return r;
+  if (pos < 0 || pos + 1 > max_seq)
+    return set_err(5, "%s: pos %d outside the cache (max_seq %d)", who, pos,
+                   max_seq);
+  if (window < 0) return set_err(5, "%s: window %d < 0", who, window);
+  if (nlaunch < 1 || nlaunch > 16)
+    return set_err(5, "%s: nlaunch %d outside [1,16]", who, nlaunch);
+  for (int i = 0; i < nlaunch; ++i)
+    if (nchunks[i] < 1 || nchunks[i] > 64)
+      return set_err(5, "%s: nchunk %d outside [1,64]", who, nchunks[i]);
+  OpBufs b;
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreate(&b.s));
+  const int Sq = nh * hd;
+  const size_t ncache = (size_t)nkv * max_seq * hd;
+  u16 *dq, *dkc, *dvc;
+  void *dout, *dws, *dcnt, *dpos;
+  if ((r = ob_up16(b, q, Sq, &dq))) return r;
+  if ((r = ob_up16(b, kc, ncache, &dkc))) return r;
+  if ((r = ob_up16(b, vc, ncache, &dvc))) return r;
+  if ((r = ob_alloc(b, &dout, (size_t)nlaunch * Sq * 2))) return r;
+  if ((r = ob_alloc(b, &dws, (size_t)nh * 64 * (hd + 4) * 4))) return r;
+  if ((r = ob_alloc(b, &dcnt, (size_t)nh * 4))) return r;
+  if ((r = ob_upf32(b, &pos, sizeof(int), &dpos))) return r;
+  HIP_TRY(hipMemsetAsync(dout, 0, (size_t)nlaunch * Sq * 2, b.s));
+  HIP_TRY(hipMemsetAsync(dcnt, 0, (size_t)nh * 4, b.s));
+  for (int i = 0; i < nlaunch; ++i)
+    launch_attn_decode(dq, dkc, dvc, (const int*)dpos, (float*)dws,
+                       (u32*)dcnt, (u16*)dout + (size_t)i * Sq, nh, nkv, hd,
+                       max_seq, nchunks[i], window, b.s);
+  HIP_TRY(hipGetLastError());
+  if (cnt_out) {
+    HIP_TRY(hipMemcpyAsync(cnt_out, dcnt, (size_t)nh * 4,
+                           hipMemcpyDeviceToHost, b.s));
+    HIP_TRY(hipStreamSynchronize(b.s));
+  }
+  return ob_down16(b, (u16*)dout, (size_t)nlaunch * Sq, out);
+}
+
 // ---- linear op entries (GEMV / fp8 / GEMM) ---------------------------------
 // Same conventions as the attention entries.  Every output buffer carries
 // CAKE_HIP_OP_GUARD extra elements past its end and is pre-filled with

@@ -96,6 +96,9 @@ void launch_attn_decode(const u16* q, const u16* kc, const u16* vc,
 // grid_y of the GQA-grouped decode-attention kernel for this head geometry
 // (0 = per-head fallback kernel); the engine's chunk-count policy uses it.
 int attn_decode_grid_y(int nh, int nkv, int hd);
+// which kernel launch_attn_decode runs for (geometry, nchunk): 0 per-head,
+// 1 grouped, 2 short-context in-block split-KV (CAKE_ATTN_SHORT=0 -> 1)
+int attn_decode_path(int nh, int nkv, int hd, int nchunk);
 // ws: split-KV partial workspace (nh * S * 2 * 132 f32) or nullptr to
 // force the single-pass path
 void launch_attn_prefill(const u16* qkv, const u16* kc, const u16* vc,

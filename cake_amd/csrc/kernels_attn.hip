@@ -963,6 +963,201 @@ __global__ __launch_bounds__(256) void k_attn_decode_g(
 #undef WS_LOAD
 }
 
+// ---------------------------------------------------------------------------
+// Short-context grouped decode attention (hd == 128, G % 4 == 0, nchunk 4|8):
+// ALL chunks of a q head live in ONE workgroup, so the split-KV combine goes
+// through LDS — no ws, no arrival counter, no atomic, no poll, no fence.
+//
+// Why: with one 64-position tile per chunk (context < 512) k_attn_decode_g
+// is ~1 us of arithmetic behind five or six dependent global round trips
+// (q -> barrier -> K/V -> publish sc1 -> returning atomic -> poll -> two
+// rounds of uncached partial loads).  Here the only global round trips are
+// pos, then {q, K, V} together, then the store.
+//
+//   grid nh * NCH / 16, block 1024 = 16 waves; wave = (head hs, chunk c),
+//   HPB = 16 / NCH heads per block (NCH 4: the four heads of a kv quad;
+//   NCH 8: two of them).  The HPB waves that share chunk c stage its tile
+//   together (64 / HPB rows each, b128 register-staged, issued at kernel
+//   entry BEFORE anything waits on q), into ONE 16 KiB LDS image per chunk
+//   that holds the K tile for phase A and is then overwritten with the V
+//   tile (already in registers) for phase C — 8 x 16 KiB fits the 160 KiB
+//   LDS where separate K and V images would not.
+//
+// Arithmetic per wave is k_attn_decode_g<4>'s, operation for operation
+// (same chunk partition, same 128-term dot order, same wave_max / wave_sum /
+// __expf online softmax per tile, same PV order, same combine chain with
+// clamped chunks weighted 0), so the output is bit-identical to it at the
+// same (n, nchunk, window); tests/test_attn_short_gpu.py asserts that.
+// A chunk may hold several tiles (a graph captured at nchunk 4 runs to
+// position ~319): the tile loop carries (m, l, o) exactly as the grouped
+// kernel does, with the next tile's loads in flight under phase C.
+// ---------------------------------------------------------------------------
+template <int NCH>
+__global__ __launch_bounds__(1024) void k_attn_decode_short(
+    const u16* __restrict__ q, const u16* __restrict__ kc,
+    const u16* __restrict__ vc, const int* __restrict__ pos,
+    u16* __restrict__ outbuf, int nh, int nkv, int max_seq, int window) {
+  constexpr int TILE = 64;
+  constexpr int HPB = 16 / NCH;  // q heads per block = waves per chunk
+  constexpr int NL = 16 / HPB;   // 16-B units per lane per tile image
+  // NCH 8 stages 64 VGPRs per wave inside the 128-VGPR budget of a 16-wave
+  // block: fully unrolled phases spilled (up to 30 VGPRs to scratch), these
+  // factors are the largest that do not
+  constexpr int UA = NCH == 8 ? 8 : 16, UC = NCH == 8 ? 4 : 8;
+  const int hd = 128;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  u16* tiles = reinterpret_cast<u16*>(smem);               // [NCH][TILE][128]
+  float* sc = reinterpret_cast<float*>(smem + NCH * TILE * 256);  // [16][TILE]
+  float* qlds = sc + 16 * TILE;                            // [HPB][128] f32
+  float* po = qlds + HPB * 128;                            // [16][128]
+  float* pm = po + 16 * 128;                               // [16]
+  float* pl = pm + 16;                                     // [16]
+
+  const int G = nh / nkv;
+  const int quad = blockIdx.x / (4 / HPB), part = blockIdx.x % (4 / HPB);
+  const int kvh = quad / (G / 4), sub = quad % (G / 4);
+  const int h0 = kvh * G + sub * 4 + part * HPB;
+  const int t = threadIdx.x, wid = t / WAVE, lane = t % WAVE;
+  const int hs = wid / NCH;   // the head this wave serves
+  const int chunk = wid % NCH;
+  const int n = *pos + 1;
+  const int lo = (window > 0 && n > window) ? n - window : 0;
+  const int cs = (n - lo + NCH - 1) / NCH;
+  const int start = lo + chunk * cs;
+  const int end = min(start + cs, n);
+  const float scale = rsqrtf(128.f);
+  const u16* kbase = kc + (size_t)kvh * max_seq * hd;
+  const u16* vbase = vc + (size_t)kvh * max_seq * hd;
+  u16* tcur = tiles + (size_t)chunk * TILE * 128;
+
+  // same staging image as k_attn_decode_g: K XOR-unit swizzled, V linear,
+  // overshoot rows collapsed onto row end-1 (>= 0 even for an empty chunk,
+  // so every load below is in range and needs no predicate)
+  short8 rk[NL], rv[NL];
+  auto stage_load = [&](short8 (&regs)[NL], const u16* base, int tb,
+                        bool swz) {
+#pragma unroll
+    for (int j = 0; j < NL; ++j) {
+      const int r = (hs * NL + j) * 4 + (int)(lane >> 4);
+      const int row = min(tb + r, end - 1);
+      const int unit = swz ? ((lane & 15) ^ (r & 15)) : (lane & 15);
+      regs[j] = *reinterpret_cast<const short8*>(base + (size_t)row * 128 +
+                                                 unit * 8);
+    }
+  };
+  auto stage_write = [&](short8 (&regs)[NL]) {
+#pragma unroll
+    for (int j = 0; j < NL; ++j)
+      *reinterpret_cast<short8*>(tcur + (size_t)(hs * NL + j) * 4 * 128 +
+                                 lane * 8) = regs[j];
+  };
+
+  // ONE round trip for q, K and V of the first tile: nothing waits in between
+  // (q is loaded by every thread at a clamped index: a load under a
+  // divergent branch gets its own vmcnt(0) before the branch rejoins;
+  // hipcc still issues it BEHIND the tile loads, so the waves that write q
+  // to LDS wait for V as well — all of it is one round trip regardless)
+  const u16 qv = q[(size_t)(h0 + min(t / 128, HPB - 1)) * hd + (t & 127)];
+  stage_load(rk, kbase, start, true);
+  stage_load(rv, vbase, start, false);
+  if (t < HPB * 128) qlds[t] = b2f(qv);
+
+  float m = -INFINITY, lsum = 0.f, o0 = 0.f, o1 = 0.f;
+  const int nt = start < end ? (end - start + TILE - 1) / TILE : 0;
+  const int ntmax = (cs + TILE - 1) / TILE;  // chunk 0's count: block-uniform
+  for (int ti = 0; ti < ntmax; ++ti) {
+    const int tb = start + ti * TILE;
+    stage_write(rk);
+    __syncthreads();  // K image (and q) visible
+    if (ti < nt) {
+      // ---- A: lane = position, full 128-dot ------------------------------
+      float d = 0.f;
+#pragma unroll UA
+      for (int u = 0; u < 16; ++u) {
+        short8 kv8 = *reinterpret_cast<const short8*>(
+            tcur + (size_t)lane * 128 + ((u ^ (lane & 15)) * 8));
+        f32x4 q0 = *reinterpret_cast<const f32x4*>(qlds + hs * 128 + u * 8);
+        f32x4 q1 = *reinterpret_cast<const f32x4*>(
+            qlds + hs * 128 + u * 8 + 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          d = fmaf(b2f((u16)kv8[e]), q0[e], d);
+          d = fmaf(b2f((u16)kv8[e + 4]), q1[e], d);
+        }
+      }
+      // ---- B: online softmax ---------------------------------------------
+      const float sv = (tb + lane < end) ? d * scale : -INFINITY;
+      float tm = wave_max(sv);
+      tm = __shfl(tm, 0, WAVE);
+      const float mnew = fmaxf(m, tm);
+      const float alpha = (mnew == -INFINITY) ? 0.f : __expf(m - mnew);
+      const float ew = (sv == -INFINITY) ? 0.f : __expf(sv - mnew);
+      float ts = wave_sum(ew);
+      ts = __shfl(ts, 0, WAVE);
+      lsum = lsum * alpha + ts;
+      o0 *= alpha;
+      o1 *= alpha;
+      m = mnew;
+      sc[wid * TILE + lane] = ew;  // the wave's own row; C reads it broadcast
+    }
+    __syncthreads();  // every wave is done with the K image
+    stage_write(rv);
+    if (ti + 1 < ntmax) {  // next tile's loads fly under phase C
+      stage_load(rk, kbase, tb + TILE, true);
+      stage_load(rv, vbase, tb + TILE, false);
+    }
+    __syncthreads();  // V image visible
+    if (ti < nt) {
+      // ---- C: PV accumulate, lane = dim pair -----------------------------
+#pragma unroll UC
+      for (int p8 = 0; p8 < TILE; p8 += 8) {
+        f32x4 w0 = *reinterpret_cast<const f32x4*>(sc + wid * TILE + p8);
+        f32x4 w1 = *reinterpret_cast<const f32x4*>(sc + wid * TILE + p8 + 4);
+        u32 vv[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          vv[e] = *reinterpret_cast<const u32*>(
+              tcur + (size_t)(p8 + e) * 128 + 2 * lane);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float wt = e < 4 ? w0[e] : w1[e - 4];
+          o0 = fmaf(wt, b2f((u16)(vv[e] & 0xffffu)), o0);
+          o1 = fmaf(wt, b2f((u16)(vv[e] >> 16)), o1);
+        }
+      }
+    }
+    if (ti + 1 < ntmax) __syncthreads();  // V image consumed before next K
+  }
+
+  // ---- in-block split-KV combine through LDS -------------------------------
+  po[wid * 128 + 2 * lane] = o0;
+  po[wid * 128 + 2 * lane + 1] = o1;
+  if (lane == 0) {
+    pm[wid] = m;
+    pl[wid] = lsum;
+  }
+  __syncthreads();
+  if (chunk < 2) {  // two waves per head, 64 dims each
+    const int hw = hs * NCH;
+    const float mc = lane < NCH ? pm[hw + lane] : -INFINITY;
+    const float lc = lane < NCH ? pl[hw + lane] : 0.f;
+    float M = wave_max(mc);
+    M = __shfl(M, 0, WAVE);
+    const float wc = (mc == -INFINITY) ? 0.f : __expf(mc - M);
+    float L = wave_sum(lc * wc);
+    L = __shfl(L, 0, WAVE);
+    const int d = chunk * 64 + lane;
+    float o = 0.f;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      const int cc = min(c, NCH - 1);
+      const float w = c < NCH ? __shfl(wc, c, WAVE) : 0.f;
+      o = fmaf(po[(hw + cc) * 128 + d], w, o);
+    }
+    outbuf[(size_t)(h0 + hs) * hd + d] = f2b(o / L);
+  }
+}
+
 // grouped-kernel dispatch: grid_y (nkv * subg) when the GQA-grouped decode
 // kernel applies to this head geometry, 0 = fall back to the per-head
 // kernel.  The engine uses this for its split-KV chunk-count policy.
@@ -973,6 +1168,23 @@ int attn_decode_grid_y(int nh, int nkv, int hd) {
   if (G >= 4 && G % 4 == 0) return nkv * (G / 4);
   if (G == 2 || G == 1) return nkv;
   return 0;
+}
+
+// which decode kernel launch_attn_decode runs: 0 = per-head
+// (k_attn_decode_fused), 1 = grouped (k_attn_decode_g), 2 = short
+// (k_attn_decode_short).  The short kernel is routed at nchunk 4 only: at
+// nchunk 8 (two heads per block, 144 KiB of LDS, reduced unrolls) it
+// measured no faster than the grouped kernel per launch and slower end to
+// end (profiles/short_attn_NOTES.md), so there it runs only under
+// CAKE_ATTN_SHORT=2.  CAKE_ATTN_SHORT=0 restores the grouped routing
+// everywhere.  The knob is read per launch so a test can flip it.
+int attn_decode_path(int nh, int nkv, int hd, int nchunk) {
+  if (attn_decode_grid_y(nh, nkv, hd) <= 0) return 0;
+  const char* e = getenv("CAKE_ATTN_SHORT");
+  const int mode = e ? atoi(e) : 1;
+  if (mode == 0 || (nh / nkv) % 4 != 0) return 1;
+  if (nchunk == 4 || (nchunk == 8 && mode >= 2)) return 2;
+  return 1;
 }
 
 // ---------------------------------------------------------------------------
@@ -1475,6 +1687,31 @@ void launch_attn_decode(const u16* q, const u16* kc, const u16* vc,
                         int nkv, int hd, int max_seq, int nchunk, int window,
                         hipStream_t s) {
   const int gy = attn_decode_grid_y(nh, nkv, hd);
+  if (attn_decode_path(nh, nkv, hd, nchunk) == 2) {
+    // tile image per chunk + scores[16][64] + q f32 [HPB][128] + partial
+    // o [16][128] + m/l [16] each
+    const size_t smem = (size_t)nchunk * 64 * 256 + 16 * 64 * 4 +
+                        (size_t)(16 / nchunk) * 128 * 4 + 16 * 128 * 4 +
+                        2 * 16 * 4;
+    static bool attr = false;
+    if (!attr) {
+      hipFuncSetAttribute((const void*)&k_attn_decode_short<4>,
+                          hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+      hipFuncSetAttribute((const void*)&k_attn_decode_short<8>,
+                          hipFuncAttributeMaxDynamicSharedMemorySize,
+                          144 * 1024);
+      attr = true;
+    }
+    if (nchunk == 4)
+      hipLaunchKernelGGL(k_attn_decode_short<4>, dim3(nh / 4), dim3(1024),
+                         smem, s, q, kc, vc, pos, out, nh, nkv, max_seq,
+                         window);
+    else
+      hipLaunchKernelGGL(k_attn_decode_short<8>, dim3(nh / 2), dim3(1024),
+                         smem, s, q, kc, vc, pos, out, nh, nkv, max_seq,
+                         window);
+    return;
+  }
   if (gy > 0) {
     const int G = nh / nkv;
     const int GB = (G >= 4) ? 4 : G;

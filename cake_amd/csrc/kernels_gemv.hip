@@ -51,6 +51,17 @@ __global__ __launch_bounds__(256) void k_gemv_reg(
       if (k0 < K) xpre[i] = *reinterpret_cast<const short8*>(x + k0);
     }
   }
+  // EPI == 1: the residual element of the row this thread will store,
+  // requested here instead of after the final barrier (one dependent round
+  // trip at the tail of every block).  The product passes res == out
+  // (e->x, in place) although both are __restrict__: the early read is safe
+  // because row `row0 + t` is read here and written in the epilogue by this
+  // SAME thread and by no other block — keep it that way.  Every thread
+  // loads (clamped to the block's last live row; only t < ROWS uses it): a
+  // load under `if (t < ROWS)` would get its own vmcnt(0) drain.
+  u16 respre = 0;
+  if constexpr (EPI == 1)
+    respre = res[min(row0 + min(t, ROWS - 1), N - 1)];
   short8 nwpre[NORM ? KB : 1];
   if (NORM) {
 #pragma unroll
@@ -164,7 +175,7 @@ __global__ __launch_bounds__(256) void k_gemv_reg(
       if (EPI == 2) {
         reinterpret_cast<float*>(out)[row] = v;
       } else if (EPI == 1) {
-        reinterpret_cast<u16*>(out)[row] = f2b(v + b2f(res[row]));
+        reinterpret_cast<u16*>(out)[row] = f2b(v + b2f(respre));
       } else {
         reinterpret_cast<u16*>(out)[row] = f2b(v);
       }
@@ -320,6 +331,23 @@ __global__ __launch_bounds__(256) void k_gemv_qkv_rope(
         wpre[r][i] = ntload8(W + (size_t)rows[r] * K + k0c);
       }
   }
+  // The epilogue's operands: pos, then this block's two cos/sin pairs (a
+  // fresh cache line every step).  They used to be read by thread 0 AFTER
+  // the final barrier — two dependent round trips at the tail of every
+  // block; requested here they land under the weight stream and the
+  // epilogue runs from registers.  V blocks need none and read pair 0
+  // (i0 == 0), which keeps the loads branch-free.  Placed BEHIND the vector
+  // load issue: ahead of it, hipcc parks every x/weight load behind the
+  // scalar wait on pos.
+  const int p = *pos;
+  const float rc0 = cost[(size_t)p * half + i0];
+  const float rc1 = cost[(size_t)p * half + i0 + 1];
+  const float rs0 = sint[(size_t)p * half + i0];
+  const float rs1 = sint[(size_t)p * half + i0 + 1];
+  // pin the loads HERE: the tables are read-only __restrict__, so hipcc
+  // otherwise sinks them back into thread 0's epilogue branch, behind the
+  // final barrier
+  asm volatile("" ::"s"(rc0), "s"(rc1), "s"(rs0), "s"(rs1));
 
   float xr[KB * 8];
 #pragma unroll
@@ -391,7 +419,6 @@ __global__ __launch_bounds__(256) void k_gemv_qkv_rope(
 #pragma unroll
     for (int r = 0; r < 4; ++r)
       s[r] = red[r][0] + red[r][1] + red[r][2] + red[r][3];
-    const int p = *pos;
     if (isv) {
       const int kvh = (rows[0] - (nh + nkv) * hd) / hd;
       const int d0 = rows[0] % hd;
@@ -404,13 +431,11 @@ __global__ __launch_bounds__(256) void k_gemv_qkv_rope(
         dstt[(size_t)r * max_seq] = bv;
       }
     } else {
-      const float* c = cost + (size_t)p * half + i0;
-      const float* sn = sint + (size_t)p * half + i0;
       u16 o[4];
-      o[0] = f2b(s[0] * c[0] - s[2] * sn[0]);
-      o[1] = f2b(s[1] * c[1] - s[3] * sn[1]);
-      o[2] = f2b(s[2] * c[0] + s[0] * sn[0]);
-      o[3] = f2b(s[3] * c[1] + s[1] * sn[1]);
+      o[0] = f2b(s[0] * rc0 - s[2] * rs0);
+      o[1] = f2b(s[1] * rc1 - s[3] * rs1);
+      o[2] = f2b(s[2] * rc0 + s[0] * rs0);
+      o[3] = f2b(s[3] * rc1 + s[1] * rs1);
       if (head < nh) {  // q -> activation buffer, in place
         u16* q = out + (size_t)head * hd + i0;
         q[0] = o[0];
@@ -533,6 +558,21 @@ __global__ __launch_bounds__(256) void k_gemv_gateup(
       }
     }
   }
+  // KB == 2 with NORM (the 8B decode shape): the i == 0 slab's weight loads
+  // go out here, ahead of the norm's two barriers, as k_gemv_reg does for
+  // KB <= 2 — otherwise every block sits through the x round trip and the
+  // reduction before its first weight byte is requested.
+  constexpr bool PRE = NORM && KB == 2;
+  short8 gpre[PRE ? ROWS : 1], upre[PRE ? ROWS : 1];
+  if constexpr (PRE) {
+    const int k0c = max(0, min(t * 8, K - 8));
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+      const int rc = min(c0 + r, I - 1);
+      gpre[r] = ntload8(W + (size_t)rc * K + k0c);
+      upre[r] = ntload8(W + (size_t)(rc + I) * K + k0c);
+    }
+  }
   float xr[KB * 8];
 #pragma unroll
   for (int i = 0; i < KB; ++i) {
@@ -574,6 +614,11 @@ __global__ __launch_bounds__(256) void k_gemv_gateup(
       short8 gv[ROWS], uv[ROWS];
 #pragma unroll
       for (int r = 0; r < ROWS; ++r) {
+        if (PRE && i == 0) {
+          gv[r] = gpre[r];
+          uv[r] = upre[r];
+          continue;
+        }
         const int rc = min(c0 + r, I - 1);
         gv[r] = ntload8(W + (size_t)rc * K + k0c);
         uv[r] = ntload8(W + (size_t)(rc + I) * K + k0c);

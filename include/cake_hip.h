@@ -188,6 +188,20 @@ int cake_hip_op_attn_decode(int nh, int nkv, int hd, int max_seq, int pos,
  * for decode at this head geometry: out = {pfv, nw, split, deep,
  * split_min_s, decode grid_y (0 = per-head kernel)}. */
 int cake_hip_attn_dispatch(int S, int nh, int nkv, int hd, int out[6]);
+/* Host only: the decode-attention kernel the product launches for this head
+ * geometry and chunk count: 0 = per-head, 1 = grouped, 2 = short-context
+ * (all chunks of a head in one workgroup; nchunk 4).  CAKE_ATTN_SHORT, read on
+ * every call: 0 = never the short kernel, 2 = also at nchunk 8. */
+int cake_hip_attn_decode_path(int nh, int nkv, int hd, int nchunk);
+/* cake_hip_op_attn_decode with a chunk count PER LAUNCH: nlaunch (1..16)
+ * launches back to back on one set of buffers, launch i split over
+ * nchunks[i]; out is (nlaunch, nh*hd).  cnt_out (nh words, may be NULL)
+ * receives the arrival counters after the last launch; they start at 0. */
+int cake_hip_op_attn_decode_seq(int nh, int nkv, int hd, int max_seq, int pos,
+                                int window, int nlaunch, const int *nchunks,
+                                const float *q, const float *kc,
+                                const float *vc, float *out,
+                                uint32_t *cnt_out, int device);
 
 /* Linear-layer op entries (test-only): GEMV, fp8 GEMV, gate-up, fused
  * qkv-rope, prefill GEMM, fp8 dequant.  Conventions of the attention entries
