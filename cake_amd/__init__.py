@@ -85,6 +85,14 @@ def _load_lib():
     lib.cake_hip_linear_dispatch.argtypes = [c, c, c, c, c,
                                              ctypes.POINTER(c)]
     lib.cake_hip_decode_dispatch.argtypes = [cp, ctypes.POINTER(c)]
+    i32p = ctypes.POINTER(ctypes.c_int32)
+    lib.cake_hip_op_gemv_w4.argtypes = [c] * 7 + [fp, i32p, i32p, fp, fp, fp,
+                                                  c]
+    lib.cake_hip_op_gemv_gateup_w4.argtypes = [c] * 4 + [fp, i32p, i32p, fp,
+                                                         fp, c]
+    lib.cake_hip_op_dequant_w4.argtypes = [c] * 3 + [i32p, i32p, fp, fp, c]
+    lib.cake_hip_linear_dispatch_w4.argtypes = [c, c, c, c,
+                                                ctypes.POINTER(c)]
     lib.cake_hip_kernel_stats.argtypes = [p, ctypes.c_char_p, c]
     lib.cake_hip_stats_reset.argtypes = [p]
     lib.cake_hip_set_stats.argtypes = [p, c]
@@ -326,7 +334,8 @@ OP_SENTINEL = -2.0 ** 60     # what outputs and guards are pre-filled with
 GEMV_KINDS = {"bf16": 0, "fp8": 1, "splitk": 2}
 GEMM_VARIANTS = {"128": 0, "256": 1, "128x256": 2, "256p": 3, "library": 4}
 LINEAR_FAMILIES = ("gemv_reg", "gemv_stream", "gemv_fp8", "gemv_fp8_stream",
-                   "gateup", "gateup_fp8", "qkv_rope", "splitk", "gemm")
+                   "gateup", "gateup_fp8", "qkv_rope", "splitk", "gemm",
+                   "gemv_w4", "gateup_w4")
 LINEAR_KINDS = {"plain": 0, "gateup": 1, "qkv_rope": 2, "splitk": 3,
                 "gemm": 4}
 
@@ -517,6 +526,79 @@ def linear_dispatch(kind, n, K, M=1, fp8=False):
         d = dict(family="gemm", lib_first=bool(o[3]),
                  variant=list(GEMM_VARIANTS)[o[4]])
     return d
+
+
+# ---- GPTQ 4-bit op entries (checkpoint-layout tensors) ---------------------
+def _i32(a, shape, name):
+    a = np.ascontiguousarray(a, dtype=np.int32)
+    if a.shape != tuple(shape):
+        raise ValueError(f"{name}: shape {a.shape}, expected {tuple(shape)}")
+    return a, a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+
+
+def _w4_tensors(qweight, qzeros, scales, group):
+    """(N, K, g, pointers) of one gptq projection in checkpoint layout:
+    qweight (K/8, N) int32, qzeros (K/g, N/8) int32, scales (K/g, N)."""
+    qweight = np.asarray(qweight)
+    K, N = qweight.shape[0] * 8, qweight.shape[1]
+    g = K if group == -1 else int(group)
+    G = K // g if g > 0 else 0
+    qw = _i32(qweight, (K // 8, N), "qweight")
+    qz = _i32(qzeros, (G, N // 8), "qzeros")
+    sc = _f32_shaped(scales, (G, N), "scales")
+    return N, K, g, qw, qz, sc
+
+
+def op_gemv_w4(x, qweight, qzeros, scales, group, epi=0, res=None, rows=0,
+               alias=False, device=0):
+    """The 4-bit GEMV on x (repeats, K) [and res (repeats, N)], one launch per
+    row back to back.  Returns (out (repeats, N), guards (repeats,
+    OP_GUARD))."""
+    N, K, g, qw, qz, sc = _w4_tensors(qweight, qzeros, scales, group)
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    x = x[None] if x.ndim == 1 else x
+    repeats = x.shape[0]
+    _, xp = _f32_shaped(x, (repeats, K), "x")
+    _r, rp = _opt_f32(res, (repeats, N), "res")
+    out = np.empty((repeats, N + OP_GUARD), dtype=np.float32)
+    _check(_lib.cake_hip_op_gemv_w4(
+        N, K, g, epi, rows, 1 if alias else 0, repeats, xp, qw[1], qz[1],
+        sc[1], rp, out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+        device))
+    return out[:, :N], out[:, N:]
+
+
+def op_gemv_gateup_w4(x, qweight, qzeros, scales, group, rows=0, device=0):
+    """The 4-bit gate-up GEMV -> silu_mul on normalized x (K,); the tensors
+    hold N = 2I columns, gate then up.  Returns (out (I,), guards)."""
+    N, K, g, qw, qz, sc = _w4_tensors(qweight, qzeros, scales, group)
+    I = N // 2
+    _, xp = _f32_shaped(np.ascontiguousarray(x, dtype=np.float32), (K,), "x")
+    out = np.empty(I + OP_GUARD, dtype=np.float32)
+    _check(_lib.cake_hip_op_gemv_gateup_w4(
+        I, K, g, rows, xp, qw[1], qz[1], sc[1],
+        out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), device))
+    return out[:I], out[I:]
+
+
+def op_dequant_w4(qweight, qzeros, scales, group, device=0):
+    """4-bit -> bf16 dequant of one projection.  Returns (out (N, K),
+    guards)."""
+    N, K, g, qw, qz, sc = _w4_tensors(qweight, qzeros, scales, group)
+    out = np.empty(N * K + OP_GUARD, dtype=np.float32)
+    _check(_lib.cake_hip_op_dequant_w4(
+        N, K, g, qw[1], qz[1], sc[1],
+        out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), device))
+    return out[:N * K].reshape(N, K), out[N * K:]
+
+
+def linear_dispatch_w4(kind, n, K, group=128):
+    """The 4-bit kernel choice (host only) for kind "plain" (n = N) or
+    "gateup" (n = I).  Returns dict(family, rows, kb)."""
+    o = (ctypes.c_int * 5)()
+    _check(_lib.cake_hip_linear_dispatch_w4(LINEAR_KINDS[kind], n, K, group,
+                                            o))
+    return dict(family=LINEAR_FAMILIES[o[0]], rows=o[1], kb=o[2])
 
 
 def decode_dispatch(config):

@@ -50,6 +50,12 @@ MISTRAL_7B = dict(
     tie_word_embeddings=False, sliding_window=4096,
 )
 
+# Llama-3-8B with AutoGPTQ 4-bit weights (group 128, no act-order): the seven
+# projections of every layer are 4-bit, embedding / lm_head / norms 16-bit
+LLAMA3_8B_GPTQ = dict(LLAMA3_8B,
+    quantization_config=dict(quant_method="gptq", bits=4, group_size=128,
+                             desc_act=False, sym=True))
+
 MODELS = {
     "llama3-8b": LLAMA3_8B,
     "llama3-70b": LLAMA3_70B,
@@ -58,6 +64,39 @@ MODELS = {
     "qwen3-32b": QWEN3_32B,
     "qwen3-32b-fp8": QWEN3_32B_FP8,
 }
+
+
+# quantized variants live beside MODELS (the pinned bf16/fp8 table)
+QUANT_MODELS = {
+    "llama3-8b-gptq": LLAMA3_8B_GPTQ,
+}
+
+
+def weight_bytes(cfg: dict, lo=0, hi=None, embed=True, head=True) -> int:
+    """Bytes of weights resident in HBM for this config: bf16, or for a gptq
+    config the device 4-bit layout (packed nibbles + an f32 {scale, zero
+    term} pair per row and group) with 16-bit embedding, head and norms."""
+    q = cfg.get("quantization_config") or {}
+    if q.get("quant_method") != "gptq":
+        return weight_bytes_bf16(cfg, lo, hi, embed, head)
+    H, I, V = cfg["hidden_size"], cfg["intermediate_size"], cfg["vocab_size"]
+    nh, nkv = cfg["num_attention_heads"], cfg["num_key_value_heads"]
+    hd = cfg.get("head_dim") or H // nh
+    L = (hi if hi is not None else cfg["num_hidden_layers"]) - lo
+    g = q.get("group_size", 128)
+
+    def w4(n, k):
+        return n * k // 2 + n * (k // (k if g == -1 else g)) * 8
+    per_layer = (w4((nh + 2 * nkv) * hd, H) + w4(H, nh * hd) +
+                 w4(2 * I, H) + w4(H, I) + 2 * H * 2)
+    total = L * per_layer
+    if embed:
+        total += V * H * 2
+    if head:
+        total += H * 2
+        if not cfg.get("tie_word_embeddings"):
+            total += V * H * 2
+    return total
 
 
 def weight_bytes_bf16(cfg: dict, lo=0, hi=None, embed=True, head=True) -> int:

@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -85,6 +86,9 @@ struct ModelConfig {
   float rms_eps = 1e-5f, rope_theta = 10000.f;
   bool tied = false, qk_norm = false;
   bool fp8 = false;  // quantization_config.quant_method == "fp8" (fp8.rs:20-40)
+  bool w4 = false;   // quant_method == "gptq", bits 4 (gptq.rs:69-86)
+  int group = 128;   // gptq group_size; -1 = one group per row
+  int grp(int K) const { return group > 0 ? group : K; }
   // llama3 rope scaling (config.rs:50-65)
   bool rope_llama3 = false;
   float rs_factor = 1, rs_low = 1, rs_high = 4;
@@ -145,8 +149,23 @@ static int parse_config(const char* json, ModelConfig* c) {
       c->mwl = first_sliding < 0 ? c->layers : first_sliding;
     }
   if (auto qc = v->get("quantization_config"))
-    if (auto qm = qc->get("quant_method"))
+    if (auto qm = qc->get("quant_method")) {
       c->fp8 = qm->str == "fp8";
+      c->w4 = qm->str == "gptq";
+      if (c->w4) {  // AutoGPTQ 4-bit, no act-order (gptq.rs:69-86)
+        int bits = 4;
+        if (auto p = qc->get("bits")) bits = (int)p->num_or(4);
+        if (bits != 4)
+          return set_err(5, "gptq: bits %d unsupported (only 4-bit)", bits);
+        if (auto p = qc->get("group_size")) c->group = (int)p->num_or(128);
+        if (c->group == 0 || c->group < -1)
+          return set_err(5, "gptq: group_size %d", c->group);
+        if (auto p = qc->get("desc_act"))
+          if (p->bool_or(false))
+            return set_err(5, "gptq: desc_act true (act-order) is not "
+                              "supported");
+      }
+    }
   if (auto rs = v->get("rope_scaling")) {
     if (rs->kind == minijson::Value::Obj) {
       auto ty = rs->get("rope_type");
@@ -163,6 +182,34 @@ static int parse_config(const char* json, ModelConfig* c) {
   }
   if (!c->hidden || !c->vocab || !c->layers || !c->nh)
     return set_err(5, "config.json: missing required fields");
+  return 0;
+}
+
+// gptq shape rules of the 4-bit kernels (host only; engine create and the
+// dispatch query): a lane's 32-k span must lie in one group, zero points pack
+// 8 output columns per word, and the register GEMV covers K <= 32768
+static int w4_dim_err(const char* name, int N, int K, int g) {
+  if (K < 32 || K > 32768)
+    return set_err(5, "gptq: %s in_features %d outside [32, 32768]", name, K);
+  if (g < 32 || g % 32 != 0)
+    return set_err(5, "gptq: group_size %d (of %s) must be a positive "
+                   "multiple of 32", g, name);
+  if (K % g != 0)
+    return set_err(5, "gptq: %s in_features %d is not a multiple of "
+                   "group_size %d", name, K, g);
+  if (N < 8 || N % 8 != 0)
+    return set_err(5, "gptq: %s out_features %d is not a multiple of 8",
+                   name, N);
+  return 0;
+}
+static int w4_config_err(const ModelConfig& c) {
+  const int H = c.hidden, I = c.inter, Sq = c.sq(), Skv = c.skv();
+  int r;
+  if ((r = w4_dim_err("q_proj", Sq, H, c.grp(H)))) return r;
+  if ((r = w4_dim_err("k_proj/v_proj", Skv, H, c.grp(H)))) return r;
+  if ((r = w4_dim_err("o_proj", H, Sq, c.grp(Sq)))) return r;
+  if ((r = w4_dim_err("gate_proj/up_proj", I, H, c.grp(H)))) return r;
+  if ((r = w4_dim_err("down_proj", H, I, c.grp(I)))) return r;
   return 0;
 }
 
@@ -239,6 +286,10 @@ struct LayerDev {
   unsigned char *wqkv8 = nullptr, *wo8 = nullptr, *wgu8 = nullptr,
                 *wdown8 = nullptr;
   float *sqkv = nullptr, *so8 = nullptr, *sgu = nullptr, *sdown = nullptr;
+  // gptq 4-bit weights (kernels_w4.hip layout: out-major packed nibbles,
+  // K/8 words per row) + per-row (N, G) f32 pairs {s, -(z+1)*s}
+  u32 *wqkv4 = nullptr, *wo4 = nullptr, *wgu4 = nullptr, *wdown4 = nullptr;
+  float *zqkv = nullptr, *zo = nullptr, *zgu = nullptr, *zdown = nullptr;
 };
 
 struct cake_engine {
@@ -257,7 +308,7 @@ struct cake_engine {
   // workspaces
   u16 *x = nullptr, *xn = nullptr, *qkv = nullptr, *attn_out = nullptr;
   u16 *gu = nullptr, *act = nullptr;
-  u16 *wscratch = nullptr;  // fp8 prefill: per-layer dequantized weight
+  u16 *wscratch = nullptr;  // fp8/w4 prefill: per-layer dequantized weight
   float* logits = nullptr;
   float* fbuf = nullptr;
   u32* ids = nullptr;
@@ -402,11 +453,16 @@ static void stats_flush(cake_engine* e) {
   e->st.pool_used = 0;
 }
 
-// Full-rotation models without qk-norm and without fp8 weights take the
+// Full-rotation models without qk-norm and without fp8/4-bit weights take the
 // fused rms_norm -> qkv GEMV -> rope -> KV-store kernel (the QK-norm rows
 // exist exactly when c.qk_norm).  Shared with cake_hip_decode_dispatch.
+// algorithmic bytes of one packed 4-bit tensor: nibbles + {s, -(z+1)s} pairs
+static double w4_bytes(double N, double K, double g) {
+  return N * K * 0.5 + N * (K / g) * 8.0;
+}
 static bool fused_qkv_rope_applies(const ModelConfig& c) {
-  return !c.fp8 && !c.qk_norm && c.hd() % 4 == 0 && c.nqkv() % 4 == 0;
+  return !c.fp8 && !c.w4 && !c.qk_norm && c.hd() % 4 == 0 &&
+         c.nqkv() % 4 == 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -429,6 +485,21 @@ static void enqueue_layer_decode(cake_engine* e, LayerDev& l,
     launch_gemv_qkv_rope(l.wqkv, e->x, e->qkv, l.rms1, c.rms_eps, l.kc,
                          l.vc, l.vtc, e->cos_t, e->sin_t, e->dev_pos, c.nh,
                          c.nkv, hd, e->max_seq, H, e->stream);
+  } else if (c.w4) {  // split norm -> 4-bit GEMV -> rope + KV store
+    {
+      StatScope ss(e, "rmsnorm", 2.0 * H * 2, 0);
+      launch_rmsnorm(e->x, l.rms1, e->xn, 1, H, c.rms_eps, e->stream);
+    }
+    {
+      StatScope ss(e, "gemv_w4", w4_bytes(Nq, H, c.grp(H)) + H * 2 + Nq * 2,
+                   2.0 * Nq * H);
+      launch_gemv_w4(l.wqkv4, l.zqkv, e->xn, e->qkv, nullptr, Nq, H,
+                     c.grp(H), 0, e->stream);
+    }
+    StatScope ss(e, "rope_store", 0, 0);
+    launch_rope_store_decode(e->qkv, l.kc, l.vc, l.vtc, e->cos_t, e->sin_t,
+                             e->dev_pos, c.nh, c.nkv, hd, hd, e->max_seq,
+                             l.qnorm, l.knorm, c.rms_eps, e->stream);
   } else {
     {  // rms_1 fused into the qkv projection (GEMV, x kept in registers)
       double wb = (double)Nq * H * (c.fp8 ? 1 : 2);
@@ -472,7 +543,12 @@ static void enqueue_layer_decode(cake_engine* e, LayerDev& l,
                        e->attn_cnt, e->attn_out, c.nh, c.nkv, hd, e->max_seq,
                        e->nchunk, c.win_for(l.idx), e->stream);
   }
-  {  // o projection + residual
+  if (c.w4) {  // o projection + residual (aliased)
+    StatScope ss(e, "gemv_w4", w4_bytes(H, Sq, c.grp(Sq)) + Sq * 2 + H * 4,
+                 2.0 * H * Sq);
+    launch_gemv_w4(l.wo4, l.zo, e->attn_out, e->x, e->x, H, Sq, c.grp(Sq), 1,
+                   e->stream);
+  } else {  // o projection + residual
     double wb = (double)H * Sq * (c.fp8 ? 1 : 2);
     StatScope ss(e, "gemv_o", wb + Sq * 2 + H * 4, 2.0 * H * Sq);
     if (c.fp8) {
@@ -492,6 +568,23 @@ static void enqueue_layer_decode(cake_engine* e, LayerDev& l,
     else
       launch_gemv(l.wo, e->attn_out, e->x, e->x, nullptr, 0.f, H, Sq, 1,
                   e->stream);
+  }
+  if (c.w4) {  // split norm, gate_up GEMV + silu_mul, down + residual
+    {
+      StatScope ss(e, "rmsnorm", 2.0 * H * 2, 0);
+      launch_rmsnorm(e->x, l.rms2, e->xn, 1, H, c.rms_eps, e->stream);
+    }
+    {
+      StatScope ss(e, "gemv_gateup_w4",
+                   w4_bytes(2 * I, H, c.grp(H)) + H * 2 + I * 2, 4.0 * I * H);
+      launch_gemv_gateup_w4(l.wgu4, l.zgu, e->xn, e->act, I, H, c.grp(H),
+                            e->stream);
+    }
+    StatScope ss(e, "gemv_w4", w4_bytes(H, I, c.grp(I)) + I * 2 + H * 4,
+                 2.0 * H * I);
+    launch_gemv_w4(l.wdown4, l.zdown, e->act, e->x, e->x, H, I, c.grp(I), 1,
+                   e->stream);
+    return;
   }
   {  // rms_2 fused into gate_up GEMV + silu_mul (mlp.rs:21-31)
     double wb = 2.0 * I * H * (c.fp8 ? 1 : 2);
@@ -559,6 +652,12 @@ static void enqueue_layer_prefill(cake_engine* e, LayerDev& l, int S,
     StatScope ss(e, "dequant_fp8", (double)Nq * H * 3, 0);
     launch_dequant_fp8(l.wqkv8, l.sqkv, e->wscratch, Nq, H, e->stream);
     wqkv = e->wscratch;
+  } else if (c.w4) {
+    StatScope ss(e, "dequant_w4",
+                 w4_bytes(Nq, H, c.grp(H)) + (double)Nq * H * 2, 0);
+    launch_dequant_w4(l.wqkv4, l.zqkv, e->wscratch, Nq, H, c.grp(H),
+                      e->stream);
+    wqkv = e->wscratch;
   }
   {
     StatScope ss(e, "gemm_qkv", (double)Nq * H * 2 + (double)S * (H + Nq) * 2,
@@ -583,6 +682,11 @@ static void enqueue_layer_prefill(cake_engine* e, LayerDev& l, int S,
     StatScope ss(e, "dequant_fp8", (double)H * Sq * 3, 0);
     launch_dequant_fp8(l.wo8, l.so8, e->wscratch, H, Sq, e->stream);
     wo = e->wscratch;
+  } else if (c.w4) {
+    StatScope ss(e, "dequant_w4",
+                 w4_bytes(H, Sq, c.grp(Sq)) + (double)H * Sq * 2, 0);
+    launch_dequant_w4(l.wo4, l.zo, e->wscratch, H, Sq, c.grp(Sq), e->stream);
+    wo = e->wscratch;
   }
   {
     StatScope ss(e, "gemm_o", (double)H * Sq * 2 + (double)S * (Sq + H) * 2,
@@ -596,6 +700,12 @@ static void enqueue_layer_prefill(cake_engine* e, LayerDev& l, int S,
   if (c.fp8) {
     StatScope ss(e, "dequant_fp8", 2.0 * I * H * 3, 0);
     launch_dequant_fp8(l.wgu8, l.sgu, e->wscratch, 2 * I, H, e->stream);
+    wgu = e->wscratch;
+  } else if (c.w4) {
+    StatScope ss(e, "dequant_w4",
+                 w4_bytes(2 * I, H, c.grp(H)) + 2.0 * I * H * 2, 0);
+    launch_dequant_w4(l.wgu4, l.zgu, e->wscratch, 2 * I, H, c.grp(H),
+                      e->stream);
     wgu = e->wscratch;
   }
   {
@@ -611,6 +721,12 @@ static void enqueue_layer_prefill(cake_engine* e, LayerDev& l, int S,
   if (c.fp8) {
     StatScope ss(e, "dequant_fp8", (double)H * I * 3, 0);
     launch_dequant_fp8(l.wdown8, l.sdown, e->wscratch, H, I, e->stream);
+    wdown = e->wscratch;
+  } else if (c.w4) {
+    StatScope ss(e, "dequant_w4",
+                 w4_bytes(H, I, c.grp(I)) + (double)H * I * 2, 0);
+    launch_dequant_w4(l.wdown4, l.zdown, e->wscratch, H, I, c.grp(I),
+                      e->stream);
     wdown = e->wscratch;
   }
   {
@@ -704,6 +820,7 @@ extern "C" int cake_hip_engine_create(const char* config_json, int layer_lo,
     return set_err(5, "hidden_size %d unsupported (> 16384)", c.hidden);
   if (c.hidden % 8 || c.inter % 8)
     return set_err(5, "hidden/intermediate must be multiples of 8");
+  if (c.w4 && (r = w4_config_err(c))) return r;
   if (max_seq <= 0) max_seq = c.max_pos;
   max_seq = (max_seq + 31) & ~31;  // MFMA prefill reads whole 32-pos tiles
   if (max_batch_tokens <= 0) max_batch_tokens = 2048;
@@ -741,6 +858,16 @@ extern "C" int cake_hip_engine_create(const char* config_json, int layer_lo,
       ALLOC(l.so8, float, (size_t)(H / 128) * (Sq / 128));
       ALLOC(l.sgu, float, (size_t)(2 * I / 128) * (H / 128));
       ALLOC(l.sdown, float, (size_t)(H / 128) * (I / 128));
+    } else if (c.w4) {
+      const size_t GH = H / c.grp(H), GS = Sq / c.grp(Sq), GI = I / c.grp(I);
+      ALLOC(l.wqkv4, u32, (size_t)Nq * H / 8);
+      ALLOC(l.wo4, u32, (size_t)H * Sq / 8);
+      ALLOC(l.wgu4, u32, (size_t)2 * I * H / 8);
+      ALLOC(l.wdown4, u32, (size_t)H * I / 8);
+      ALLOC(l.zqkv, float, (size_t)Nq * GH * 2);
+      ALLOC(l.zo, float, (size_t)H * GS * 2);
+      ALLOC(l.zgu, float, (size_t)2 * I * GH * 2);
+      ALLOC(l.zdown, float, (size_t)H * GI * 2);
     } else {
       ALLOC(l.wqkv, u16, (size_t)Nq * H);
       ALLOC(l.wo, u16, (size_t)H * Sq);
@@ -794,7 +921,7 @@ extern "C" int cake_hip_engine_create(const char* config_json, int layer_lo,
   ALLOC(e->attn_out, u16, (size_t)BT * Sq);
   ALLOC(e->gu, u16, (size_t)BT * 2 * I);
   ALLOC(e->act, u16, (size_t)BT * I);
-  if (c.fp8) {
+  if (c.fp8 || c.w4) {
     size_t mx = std::max((size_t)Nq * H,
                          std::max((size_t)H * Sq,
                                   std::max((size_t)2 * I * H,
@@ -871,6 +998,10 @@ extern "C" void cake_hip_engine_free(cake_engine* e) {
       hipFree(l.wqkv8); hipFree(l.wo8); hipFree(l.wgu8); hipFree(l.wdown8);
       hipFree(l.sqkv); hipFree(l.so8); hipFree(l.sgu); hipFree(l.sdown);
     }
+    if (l.wqkv4) {
+      hipFree(l.wqkv4); hipFree(l.wo4); hipFree(l.wgu4); hipFree(l.wdown4);
+      hipFree(l.zqkv); hipFree(l.zo); hipFree(l.zgu); hipFree(l.zdown);
+    }
     if (l.qnorm) { hipFree(l.qnorm); hipFree(l.knorm); }
   }
   if (e->embed) hipFree(e->embed);
@@ -906,6 +1037,43 @@ struct StTensor {
   size_t off0 = 0, off1 = 0;
 };
 
+static inline float b2f_host(u16 h) {
+  union { u32 u; float f; } v{(u32)h << 16};
+  return v.f;
+}
+// element i of an IEEE half array (possibly unaligned) as f32, exactly
+static inline float f16_at(const char* src, size_t i) {
+  _Float16 h;
+  memcpy(&h, src + i * 2, 2);
+  return (float)h;
+}
+
+// GPTQ checkpoint layout -> the device layout of kernels_w4.hip, for one
+// projection (the loader and the w4 op entries both come through here).
+//   qw (K/8, N) i32: nibble b of word [r, j] is q(k = 8r + b, j)
+//   qz (G, N/8) i32: nibble j % 8 of word [gi, j / 8] is z(gi, j)
+//   sc (G, N)   f32 (f16-representable)
+// -> W (N, K/8): row j contiguous over k, same nibble order inside a word;
+//    sz (N, G, 2) = {s, -(z+1)*s}: z + 1 may be 16 and does not wrap, words
+//    are read as unsigned so the top nibble is (w >> 28) & 0xF.
+static void w4_repack(const int32_t* qw, const int32_t* qz, const float* sc,
+                      size_t N, size_t K, size_t g, u32* W, float* sz) {
+  const size_t K8 = K / 8, G = K / g, N8 = N / 8;
+  const size_t T = 32;  // transpose in tiles: both sides stay in cache
+  for (size_t r0 = 0; r0 < K8; r0 += T)
+    for (size_t j0 = 0; j0 < N; j0 += T)
+      for (size_t r = r0; r < std::min(K8, r0 + T); ++r)
+        for (size_t j = j0; j < std::min(N, j0 + T); ++j)
+          W[j * K8 + r] = (u32)qw[r * N + j];
+  for (size_t gi = 0; gi < G; ++gi)
+    for (size_t j = 0; j < N; ++j) {
+      const u32 z = ((u32)qz[gi * N8 + j / 8] >> (4 * (j % 8))) & 0xFu;
+      const float s = sc[gi * N + j];
+      sz[(j * G + gi) * 2] = s;
+      sz[(j * G + gi) * 2 + 1] = -(float)(z + 1) * s;
+    }
+}
+
 static int upload_weight_u8(cake_engine* e, unsigned char* dst,
                             const char* filebase, const StTensor& t,
                             size_t expect_elems) {
@@ -938,6 +1106,10 @@ static int upload_scale(cake_engine* e, float* dst, const char* filebase,
       tmp[i] = v.f;
     }
     HIP_TRY(hipMemcpy(dst, tmp.data(), n * 4, hipMemcpyHostToDevice));
+  } else if (t.dtype == "F16") {
+    std::vector<float> tmp(n);
+    for (size_t i = 0; i < n; ++i) tmp[i] = f16_at(src, i);
+    HIP_TRY(hipMemcpy(dst, tmp.data(), n * 4, hipMemcpyHostToDevice));
   } else {
     return set_err(5, "scale_inv dtype %s unsupported", t.dtype.c_str());
   }
@@ -954,11 +1126,14 @@ static int upload_weight(cake_engine* e, u16* dst, const char* filebase,
   const char* src = filebase + t.off0;
   if (t.dtype == "BF16") {
     HIP_TRY(hipMemcpy(dst, src, n * 2, hipMemcpyHostToDevice));
-  } else if (t.dtype == "F32") {
+  } else if (t.dtype == "F32" || t.dtype == "F16") {
+    // F16 (GPTQ checkpoints ship F16 norms and embeddings) widens exactly
+    // to f32 and takes the same RNE path
     std::vector<u16> tmp(n);
     const float* f = reinterpret_cast<const float*>(src);
+    const bool half = t.dtype == "F16";
     for (size_t i = 0; i < n; ++i) {
-      union { float f; unsigned u; } v{f[i]};
+      union { float f; unsigned u; } v{half ? f16_at(src, i) : f[i]};
       unsigned r = ((v.u & 0x7fffffffu) > 0x7f800000u)
                        ? 0x7fc00000u
                        : v.u + 0x7fffu + ((v.u >> 16) & 1u);
@@ -1125,6 +1300,66 @@ static int load_safetensors_file(cake_engine* e, const char* path) {
   } while (0)
   int r;
   StTensor t;
+  // one gptq projection P (N out, K in, group g) -> rows [row0, row0 + N) of
+  // the fused device tensor dw / dsz
+  auto load_w4 = [&](const std::string& P, u32* dw, float* dsz, size_t row0,
+                     size_t N, size_t K, size_t g) -> int {
+    StTensor tq, tz, ts;
+    int rr = need(P + ".qweight", &tq);
+    if (rr == -1) return 0;  // lives in another shard, with its companions
+    if (rr) return rr;
+    for (auto nt : {std::make_pair(".qzeros", &tz),
+                    std::make_pair(".scales", &ts)}) {
+      rr = need(P + nt.first, nt.second);
+      if (rr == -1)
+        return set_err(4, "%s%s must be in the same file as %s.qweight",
+                       P.c_str(), nt.first, P.c_str());
+      if (rr) return rr;
+    }
+    const size_t G = K / g;
+    auto shape_is = [](const StTensor& s, size_t a, size_t b) {
+      return s.shape.size() == 2 && (size_t)s.shape[0] == a &&
+             (size_t)s.shape[1] == b;
+    };
+    auto bad = [&](const char* suf, const StTensor& s, const char* dt,
+                   size_t a, size_t b) {
+      std::string got;
+      for (long d : s.shape) got += (got.empty() ? "" : ", ") + std::to_string(d);
+      return set_err(5, "%s%s: %s (%s), expected %s (%zu, %zu)", P.c_str(),
+                     suf, s.dtype.c_str(), got.c_str(), dt, a, b);
+    };
+    if (tq.dtype != "I32" || !shape_is(tq, K / 8, N))
+      return bad(".qweight", tq, "I32", K / 8, N);
+    if (tz.dtype != "I32" || !shape_is(tz, G, N / 8))
+      return bad(".qzeros", tz, "I32", G, N / 8);
+    const bool sdt = ts.dtype == "F16" || ts.dtype == "BF16" ||
+                     ts.dtype == "F32";
+    if (!sdt || !shape_is(ts, G, N)) return bad(".scales", ts, "F16", G, N);
+    std::vector<int32_t> qw(K / 8 * N), qz(G * (N / 8));
+    memcpy(qw.data(), base + tq.off0, qw.size() * 4);
+    memcpy(qz.data(), base + tz.off0, qz.size() * 4);
+    std::vector<float> sc(G * N);
+    const char* sp = base + ts.off0;
+    for (size_t i = 0; i < sc.size(); ++i) {
+      if (ts.dtype == "F16") {
+        sc[i] = f16_at(sp, i);
+      } else if (ts.dtype == "BF16") {
+        u16 h;
+        memcpy(&h, sp + i * 2, 2);
+        sc[i] = b2f_host(h);
+      } else {
+        memcpy(&sc[i], sp + i * 4, 4);
+      }
+    }
+    std::vector<u32> W(N * (K / 8));
+    std::vector<float> sz(N * G * 2);
+    w4_repack(qw.data(), qz.data(), sc.data(), N, K, g, W.data(), sz.data());
+    HIP_TRY(hipMemcpy(dw + row0 * (K / 8), W.data(), W.size() * 4,
+                      hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dsz + row0 * G * 2, sz.data(), sz.size() * 4,
+                      hipMemcpyHostToDevice));
+    return 0;
+  };
   if (e->has_embed()) {
     LOADW("model.embed_tokens.weight", upload_weight(e, e->embed, base, t, V * H));
   }
@@ -1162,6 +1397,18 @@ static int load_safetensors_file(cake_engine* e, const char* path) {
       LOADW(pre + "mlp.up_proj.weight_scale_inv", upload_scale(e, l.sgu + Ib * Hb, base, t, Ib * Hb));
       LOADW(pre + "mlp.down_proj.weight", upload_weight_u8(e, l.wdown8, base, t, H * I));
       LOADW(pre + "mlp.down_proj.weight_scale_inv", upload_scale(e, l.sdown, base, t, Hb * Ib));
+    } else if (c.w4) {
+      // gptq: qweight/qzeros/scales per projection, repacked out-major at
+      // the projection's row offset of the fused tensor (g_idx and bias are
+      // ignored, as gptq.rs does)
+      const size_t gH = c.grp((int)H), gS = c.grp((int)Sq), gI = c.grp((int)I);
+      if ((r = load_w4(pre + "self_attn.q_proj", l.wqkv4, l.zqkv, 0, Sq, H, gH))) return r;
+      if ((r = load_w4(pre + "self_attn.k_proj", l.wqkv4, l.zqkv, Sq, Skv, H, gH))) return r;
+      if ((r = load_w4(pre + "self_attn.v_proj", l.wqkv4, l.zqkv, Sq + Skv, Skv, H, gH))) return r;
+      if ((r = load_w4(pre + "self_attn.o_proj", l.wo4, l.zo, 0, H, Sq, gS))) return r;
+      if ((r = load_w4(pre + "mlp.gate_proj", l.wgu4, l.zgu, 0, I, H, gH))) return r;
+      if ((r = load_w4(pre + "mlp.up_proj", l.wgu4, l.zgu, I, I, H, gH))) return r;
+      if ((r = load_w4(pre + "mlp.down_proj", l.wdown4, l.zdown, 0, H, I, gI))) return r;
     } else {
     // fused qkv: upload q,k,v at row offsets (attention.rs:109-114)
     LOADW(pre + "self_attn.q_proj.weight", upload_weight(e, l.wqkv, base, t, Sq * H));
@@ -1227,6 +1474,35 @@ extern "C" int cake_hip_init_random(cake_engine* e, uint64_t seed,
       fill_scales(l.so8, Hb * Sqb);
       fill_scales(l.sgu, 2 * Ib * Hb);
       fill_scales(l.sdown, Hb * Ib);
+    } else if (c.w4) {
+      // random nibbles, stored zero 7 (z + 1 = 8: q - 8 in [-8, 7]) and
+      // f16-representable scales around scale / 8 (+-20 %, by index), so the
+      // weights spread over about +-scale like the bf16 init
+      auto fill_sz = [&](float* p, size_t n) {
+        hscales.resize(2 * n);
+        for (size_t i = 0; i < n; ++i) {
+          const float f =
+              0.8f + 0.4f * (float)((i * 2654435761u) % 1000) / 1000.f;
+          const float sv = (float)(_Float16)(scale * 0.125f * f);
+          hscales[2 * i] = sv;
+          hscales[2 * i + 1] = -8.f * sv;
+        }
+        hipMemcpy(p, hscales.data(), 2 * n * 4, hipMemcpyHostToDevice);
+      };
+      const size_t GH = H / c.grp((int)H), GS = Sq / c.grp((int)Sq),
+                   GI = I / c.grp((int)I);
+      launch_fill_random_u32(l.wqkv4, (Sq + 2 * Skv) * H / 8,
+                             seed + 0x1000193u * base, e->stream);
+      launch_fill_random_u32(l.wo4, H * Sq / 8,
+                             seed + 0x1000193u * (base + 1), e->stream);
+      launch_fill_random_u32(l.wgu4, 2 * I * H / 8,
+                             seed + 0x1000193u * (base + 2), e->stream);
+      launch_fill_random_u32(l.wdown4, H * I / 8,
+                             seed + 0x1000193u * (base + 3), e->stream);
+      fill_sz(l.zqkv, (Sq + 2 * Skv) * GH);
+      fill_sz(l.zo, H * GS);
+      fill_sz(l.zgu, 2 * I * GH);
+      fill_sz(l.zdown, H * GI);
     } else {
       fill(l.wqkv, (Sq + 2 * Skv) * H, base);
       fill(l.wo, H * Sq, base + 1);
@@ -2433,6 +2709,143 @@ extern "C" int cake_hip_op_dequant_fp8(int N, int K, const uint8_t* w8,
   return ob_down16(b, dout, n + OPG, out);
 }
 
+// ---- 4-bit (gptq) op entries: tensors arrive in CHECKPOINT layout and go
+// through w4_repack, the loader's own routine, so the tests cover the repack
+// together with the kernels
+static int w4_op_upload(OpBufs& b, const char* who, int N, int K, int group,
+                        const int32_t* qweight, const int32_t* qzeros,
+                        const float* scales, u32** dW, float** dsz) {
+  const size_t G = (size_t)K / group;
+  std::vector<u32> W((size_t)N * (K / 8));
+  std::vector<float> sz((size_t)N * G * 2);
+  w4_repack(qweight, qzeros, scales, N, K, group, W.data(), sz.data());
+  void *pw, *ps;
+  int r;
+  if ((r = ob_upf32(b, W.data(), W.size() * 4, &pw))) return r;
+  if ((r = ob_upf32(b, sz.data(), sz.size() * 4, &ps))) return r;
+  HIP_TRY(hipStreamSynchronize(b.s));  // the staging vectors die here
+  *dW = (u32*)pw;
+  *dsz = (float*)ps;
+  (void)who;
+  return 0;
+}
+static int w4_op_args(const char* who, int N, int K, int group,
+                      const void* qweight, const void* qzeros,
+                      const void* scales, const void* out) {
+  int r = w4_dim_err(who, N, K, group);
+  if (r) return r;
+  if (!qweight || !qzeros || !scales || !out)
+    return set_err(5, "%s: qweight, qzeros, scales and out are required",
+                   who);
+  return 0;
+}
+
+extern "C" int cake_hip_op_gemv_w4(int N, int K, int group, int epi, int rows,
+                                   int alias, int repeats, const float* x,
+                                   const int32_t* qweight,
+                                   const int32_t* qzeros, const float* scales,
+                                   const float* res, float* out, int device) {
+  const char* who = "op_gemv_w4";
+  int r = w4_op_args(who, N, K, group, qweight, qzeros, scales, out);
+  if (r) return r;
+  if (!x) return set_err(5, "%s: x is required", who);
+  if (repeats < 1 || repeats > 16)
+    return set_err(5, "%s: repeats %d outside [1,16]", who, repeats);
+  if (epi < 0 || epi > 1) return set_err(5, "%s: epi %d", who, epi);
+  if (rows != 0 && rows != 4 && rows != 8)
+    return set_err(5, "%s: rows %d not in {0,4,8}", who, rows);
+  if (rows == 8 && gemv_w4_kb(K) == 8)
+    return set_err(5, "%s: rows 8 needs K <= 16384 (got %d)", who, K);
+  if ((epi == 1) != (res != nullptr))
+    return set_err(5, "%s: res goes with epi 1", who);
+  if (alias && epi != 1)
+    return set_err(5, "%s: alias needs the residual epilogue", who);
+  OpBufs b;
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreate(&b.s));
+  const size_t ld = (size_t)N + OPG;  // out row stride per repeat
+  u16 *dx, *dres = nullptr, *dout = nullptr;
+  u32* dW;
+  float* dsz;
+  if ((r = ob_up16(b, x, (size_t)repeats * K, &dx))) return r;
+  if ((r = w4_op_upload(b, who, N, K, group, qweight, qzeros, scales, &dW,
+                        &dsz)))
+    return r;
+  if ((r = ob_sent16(b, repeats * ld, &dout))) return r;
+  if (res) {
+    // residual rows at the out stride, so alias can copy them in place
+    std::vector<float> h(repeats * ld, CAKE_HIP_OP_SENTINEL);
+    for (int i = 0; i < repeats; ++i)
+      memcpy(h.data() + i * ld, res + (size_t)i * N, sizeof(float) * N);
+    if ((r = ob_up16(b, h.data(), h.size(), &dres))) return r;
+    HIP_TRY(hipStreamSynchronize(b.s));
+    if (alias) dout = dres;  // out == res, as the engine does with e->x
+  }
+  for (int i = 0; i < repeats; ++i)
+    launch_gemv_w4(dW, dsz, dx + (size_t)i * K, dout + i * ld,
+                   dres ? dres + i * ld : nullptr, N, K, group, epi, b.s,
+                   rows);
+  HIP_TRY(hipGetLastError());
+  return ob_down16(b, dout, repeats * ld, out);
+}
+
+extern "C" int cake_hip_op_gemv_gateup_w4(int I, int K, int group, int rows,
+                                          const float* x,
+                                          const int32_t* qweight,
+                                          const int32_t* qzeros,
+                                          const float* scales, float* out,
+                                          int device) {
+  const char* who = "op_gemv_gateup_w4";
+  if (I < 8 || I % 8 != 0)
+    return set_err(5, "%s: I %d is not a positive multiple of 8", who, I);
+  int r = w4_op_args(who, 2 * I, K, group, qweight, qzeros, scales, out);
+  if (r) return r;
+  if (K > 16384)
+    return set_err(5, "%s: K must be <= 16384 (got %d)", who, K);
+  if (!x) return set_err(5, "%s: x is required", who);
+  if (rows != 0 && rows != 4)
+    return set_err(5, "%s: the 4-bit gate-up kernel has 4 rows per block",
+                   who);
+  OpBufs b;
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreate(&b.s));
+  u16 *dx, *dout;
+  u32* dW;
+  float* dsz;
+  if ((r = ob_up16(b, x, K, &dx))) return r;
+  if ((r = w4_op_upload(b, who, 2 * I, K, group, qweight, qzeros, scales,
+                        &dW, &dsz)))
+    return r;
+  if ((r = ob_sent16(b, (size_t)I + OPG, &dout))) return r;
+  launch_gemv_gateup_w4(dW, dsz, dx, dout, I, K, group, b.s);
+  HIP_TRY(hipGetLastError());
+  return ob_down16(b, dout, (size_t)I + OPG, out);
+}
+
+extern "C" int cake_hip_op_dequant_w4(int N, int K, int group,
+                                      const int32_t* qweight,
+                                      const int32_t* qzeros,
+                                      const float* scales, float* out,
+                                      int device) {
+  const char* who = "op_dequant_w4";
+  int r = w4_op_args(who, N, K, group, qweight, qzeros, scales, out);
+  if (r) return r;
+  OpBufs b;
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreate(&b.s));
+  const size_t n = (size_t)N * K;
+  u32* dW;
+  float* dsz;
+  u16* dout;
+  if ((r = w4_op_upload(b, who, N, K, group, qweight, qzeros, scales, &dW,
+                        &dsz)))
+    return r;
+  if ((r = ob_sent16(b, n + OPG, &dout))) return r;
+  launch_dequant_w4(dW, dsz, dout, N, K, group, b.s);
+  HIP_TRY(hipGetLastError());
+  return ob_down16(b, dout, n + OPG, out);
+}
+
 extern "C" int cake_hip_op_silu_mul_rows(int S, int I, const float* gu,
                                          float* out, int device) {
   const char* who = "op_silu_mul_rows";
@@ -2489,8 +2902,12 @@ extern "C" int cake_hip_op_rms_norm_rows(int outer, int inner,
 // predicates enqueue_layer_decode and enqueue_head_sample use (host only):
 // out[i] = {family, rows, KB} for i = qkv, o, gate-up, down, head.  The
 // opt-in split-K residual GEMV (CAKE_GEMV_SPLITK) is not reflected.
-static void plain_dispatch(int N, int K, bool fp8, int* o) {
-  if (fp8) {
+static void plain_dispatch(int N, int K, int quant, int* o) {
+  if (quant == 2) {  // gptq 4-bit: one register family, K <= 32768
+    o[0] = CAKE_HIP_FAM_GEMV_W4;
+    o[1] = gemv_w4_rows_policy(N, K);
+    o[2] = gemv_w4_kb(K);
+  } else if (quant == 1) {
     o[2] = gemv_fp8_kb(K);
     o[0] = o[2] ? CAKE_HIP_FAM_GEMV_FP8 : CAKE_HIP_FAM_GEMV_FP8_STREAM;
     o[1] = gemv_fp8_rows_policy(N);
@@ -2506,19 +2923,22 @@ extern "C" int cake_hip_decode_dispatch(const char* config_json,
   int r = parse_config(config_json, &c);
   if (r) return r;
   const int H = c.hidden, I = c.inter;
+  if (c.w4 && (r = w4_config_err(c))) return r;
+  const int quant = c.w4 ? 2 : c.fp8 ? 1 : 0;
   if (fused_qkv_rope_applies(c)) {
     out[0] = CAKE_HIP_FAM_QKV_ROPE;
     out[1] = 4;
     out[2] = gemv_qkv_rope_kb(H);
   } else {
-    plain_dispatch(c.nqkv(), H, c.fp8, out);
+    plain_dispatch(c.nqkv(), H, quant, out);
   }
-  plain_dispatch(H, c.sq(), c.fp8, out + 3);
-  out[6] = c.fp8 ? CAKE_HIP_FAM_GATEUP_FP8 : CAKE_HIP_FAM_GATEUP;
-  out[7] = c.fp8 ? 4 : gemv_gateup_rows_policy();
-  out[8] = c.fp8 ? gemv_fp8_kb(H) : gemv_kb(H);
-  plain_dispatch(H, I, c.fp8, out + 9);
-  plain_dispatch(c.vocab, H, false, out + 12);  // lm_head stays bf16
+  plain_dispatch(H, c.sq(), quant, out + 3);
+  out[6] = c.w4 ? CAKE_HIP_FAM_GATEUP_W4
+                : c.fp8 ? CAKE_HIP_FAM_GATEUP_FP8 : CAKE_HIP_FAM_GATEUP;
+  out[7] = c.w4 || c.fp8 ? 4 : gemv_gateup_rows_policy();
+  out[8] = c.w4 ? gemv_w4_kb(H) : c.fp8 ? gemv_fp8_kb(H) : gemv_kb(H);
+  plain_dispatch(H, I, quant, out + 9);
+  plain_dispatch(c.vocab, H, 0, out + 12);  // lm_head stays bf16
   return 0;
 }
 
@@ -2531,12 +2951,16 @@ extern "C" int cake_hip_linear_dispatch(int kind, int n, int K, int M,
   if (kind < 0 || kind > 4 || n < 1 || K < 1 || M < 1)
     return set_err(5, "linear_dispatch: kind %d, n %d, K %d, M %d", kind, n,
                    K, M);
+  if (fp8 < 0 || fp8 > 1)  // the quant selector: 0 bf16, 1 fp8; w4 needs a
+                           // group size: cake_hip_linear_dispatch_w4
+    return set_err(5, "linear_dispatch: quant %d (4-bit goes through "
+                   "cake_hip_linear_dispatch_w4)", fp8);
   if (fp8 && kind >= 2)
     return set_err(5, "linear_dispatch: kind %d has no fp8 kernel", kind);
   out[0] = out[1] = out[2] = out[3] = out[4] = 0;
   switch (kind) {
     case 0:
-      plain_dispatch(n, K, fp8 != 0, out);
+      plain_dispatch(n, K, fp8, out);
       break;
     case 1:
       if (K > 16384)
@@ -2561,6 +2985,26 @@ extern "C" int cake_hip_linear_dispatch(int kind, int n, int K, int M,
       out[3] = p.lib_first ? 1 : 0;
       out[4] = p.variant;
     }
+  }
+  return 0;
+}
+
+// The 4-bit twin: kind 0 plain GEMV (n = N), 1 gate-up GEMV (n = I).
+extern "C" int cake_hip_linear_dispatch_w4(int kind, int n, int K, int group,
+                                           int out[5]) {
+  if (kind < 0 || kind > 1 || n < 1)
+    return set_err(5, "linear_dispatch_w4: kind %d, n %d", kind, n);
+  int r = w4_dim_err(kind ? "gate-up" : "gemv", n, K, group < 0 ? K : group);
+  if (r) return r;
+  out[0] = out[1] = out[2] = out[3] = out[4] = 0;
+  if (kind == 0) {
+    plain_dispatch(n, K, 2, out);
+  } else {
+    if (K > 16384)
+      return set_err(5, "linear_dispatch_w4: gate-up needs K <= 16384");
+    out[0] = CAKE_HIP_FAM_GATEUP_W4;
+    out[1] = 4;
+    out[2] = gemv_w4_kb(K);
   }
   return 0;
 }

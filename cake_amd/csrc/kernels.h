@@ -74,6 +74,22 @@ void launch_dequant_fp8(const unsigned char* W, const float* sc, u16* out,
                         int N, int K, hipStream_t s);
 void launch_fill_random_u8(unsigned char* out, size_t n, uint64_t seed,
                            hipStream_t s);
+// GPTQ 4-bit family (kernels_w4.hip).  W: out-major packed nibbles, K/8 words
+// per row; sz: (N, K/group) f32 pairs {s, -(z+1)*s}.  group % 32 == 0,
+// K % group == 0, K <= 32768.  epi 0: bf16 out; 1: bf16 out + res (res may
+// alias out).  rows_override: 4|8 rows per block, 0 = gemv_w4_rows_policy
+// (KB 8 always runs 4).  No fused norm: x is already normalized.
+int gemv_w4_kb(int K);  // 4096-wide k blocks: 1 (two half-block rows) |2|4|8
+int gemv_w4_rows_policy(int N, int K);
+void launch_gemv_w4(const u32* W, const float* sz, const u16* x, u16* out,
+                    const u16* res, int N, int K, int group, int epi,
+                    hipStream_t s, int rows_override = 0);
+// 4 channels per block; K <= 16384
+void launch_gemv_gateup_w4(const u32* W, const float* sz, const u16* x,
+                           u16* out, int I, int K, int group, hipStream_t s);
+void launch_dequant_w4(const u32* W, const float* sz, u16* out, int N, int K,
+                       int group, hipStream_t s);
+void launch_fill_random_u32(u32* out, size_t n, uint64_t seed, hipStream_t s);
 void launch_embed_token(const u16* embed, const u32* tok, u16* x, int H,
                         hipStream_t s, float* nscale = nullptr,
                         float eps = 1e-5f);

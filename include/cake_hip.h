@@ -75,7 +75,10 @@ void cake_hip_engine_free(cake_engine *e);
 /* ---- weight loading ------------------------------------------------------
  * Replaces the safetensors VarBuilder path (utils/mod.rs:251-370): mmap the
  * file, select this shard's tensors by the "model.layers.N." prefix, and
- * upload straight to HBM as bf16.  F32 and BF16 source dtypes accepted. */
+ * upload straight to HBM as bf16.  F32, F16 and BF16 source dtypes accepted.
+ * quantization_config.quant_method selects the weight format: "fp8"
+ * (weight + weight_scale_inv) or "gptq" (4-bit qweight / qzeros / scales,
+ * kept packed in HBM; bits 4, desc_act false, group_size % 32 == 0). */
 int cake_hip_load_safetensors(cake_engine *e, const char *path);
 
 /* Seeded random init on device (synthetic-weights benches; no network for
@@ -262,6 +265,32 @@ int cake_hip_op_gemm(int variant, int M, int N, int K, int epi, int alias,
  * (N*K + CAKE_HIP_OP_GUARD). */
 int cake_hip_op_dequant_fp8(int N, int K, const uint8_t *w8, const float *sc,
                             float *out, int device);
+/* GPTQ 4-bit op entries.  The tensors are in CHECKPOINT layout and pass
+ * through the loader's own repack: qweight (K/8, N) int32 (nibble b of word
+ * [r, j] is q(8r + b, j)), qzeros (K/group, N/8) int32 (nibble j % 8 of word
+ * [gi, j / 8] is z(gi, j)), scales (K/group, N) f32 holding f16-representable
+ * values; W[j, k] = (q - (z + 1)) * s.  Rules (error 5): group % 32 == 0,
+ * K % group == 0, 32 <= K <= 32768, N % 8 == 0.
+ * gemv_w4: epi 0 bf16 out, 1 bf16 out + res; rows 0 (policy) | 4 | 8 (8
+ * needs K <= 16384); alias: out == res; the kernel is launched `repeats`
+ * (1..16) times, repeat i on x row i and res row i; out is
+ * (repeats, N + CAKE_HIP_OP_GUARD). */
+int cake_hip_op_gemv_w4(int N, int K, int group, int epi, int rows, int alias,
+                        int repeats, const float *x, const int32_t *qweight,
+                        const int32_t *qzeros, const float *scales,
+                        const float *res, float *out, int device);
+/* out[c] = silu(g_c) * u_c over one fused tensor of N = 2I rows (gate rows
+ * [0, I), up rows [I, 2I)); x is already normalized.  I % 8 == 0,
+ * K <= 16384, rows 0 | 4.  out is (I + CAKE_HIP_OP_GUARD). */
+int cake_hip_op_gemv_gateup_w4(int I, int K, int group, int rows,
+                               const float *x, const int32_t *qweight,
+                               const int32_t *qzeros, const float *scales,
+                               float *out, int device);
+/* 4-bit -> bf16 (N, K) row-major, as the prefill path dequantizes into its
+ * scratch; out is (N*K + CAKE_HIP_OP_GUARD). */
+int cake_hip_op_dequant_w4(int N, int K, int group, const int32_t *qweight,
+                           const int32_t *qzeros, const float *scales,
+                           float *out, int device);
 /* Prefill silu_mul over S rows of gu (S, 2I) = [gate | up]: out[s, c] =
  * silu(gu[s, c]) * gu[s, I + c]; I % 8 == 0.  out is
  * (S*I + CAKE_HIP_OP_GUARD). */
@@ -292,9 +321,19 @@ enum {
   CAKE_HIP_FAM_QKV_ROPE = 6,
   CAKE_HIP_FAM_SPLITK = 7,
   CAKE_HIP_FAM_GEMM = 8,
+  CAKE_HIP_FAM_GEMV_W4 = 9,
+  CAKE_HIP_FAM_GATEUP_W4 = 10,
 };
+/* fp8 is the quant selector: 0 bf16, 1 fp8.  The 4-bit (gptq) kernels need a
+ * group size and are queried through cake_hip_linear_dispatch_w4. */
 int cake_hip_linear_dispatch(int kind, int n, int K, int M, int fp8,
                              int out[5]);
+/* Host only: the 4-bit kernel for kind 0 (plain GEMV, n = N) or 1 (gate-up,
+ * n = I) at this K and group size (-1 = K); out as above, KB counting
+ * 4096-wide k blocks (1 = two half-block row sets).  Error 5 when the shape
+ * breaks a rule of the 4-bit path (see cake_hip_op_gemv_w4). */
+int cake_hip_linear_dispatch_w4(int kind, int n, int K, int group,
+                                int out[5]);
 /* Host only: the five linear launches of one decode step of the model in
  * config_json, chosen by the predicates the engine itself uses: out[3*i..] =
  * {family, rows, KB} for i = qkv, o, gate-up, down, head.  The opt-in
