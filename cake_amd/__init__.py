@@ -103,6 +103,10 @@ def _load_lib():
     lib.cake_hip_op_sample.argtypes = [c, fp, f, c, f, f, u32p, c,
                                        ctypes.c_uint64, c, c, u32p,
                                        ctypes.POINTER(c), fp, c]
+    lib.cake_hip_op_argmax.argtypes = [c, fp, f, ctypes.c_uint64, c, c, c, c,
+                                       u32p, fp, i32p, u32p,
+                                       ctypes.POINTER(c), c]
+    lib.cake_hip_op_embed.argtypes = [c, c, c, c, fp, u32p, f, fp, fp, c]
     lib.cake_hip_sync.argtypes = [p]
     return lib
 
@@ -512,6 +516,67 @@ def op_rms_norm_rows(x, w, outer, inner, outer_stride, eps=1e-5, device=0):
         outer, inner, outer_stride, w.size, eps, x.size, xp, wp,
         out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), device))
     return out[:x.size], out[x.size:]
+
+
+# ---- head op entries (argmax / Gumbel draw, embedding gathers) -------------
+ARGMAX_PARTS = 256                 # launch_argmax's partition count
+OP_SENTINEL_BITS = 0xDD800000      # OP_SENTINEL as a 32-bit word
+EMBED_MODES = {"rows": 0, "token": 1, "token_nscale": 2}
+
+
+def op_argmax(logits, temperature=0.0, seed=299792458, first_step=0, steps=1,
+              ring=True, advance_pos=1, device=0):
+    """`steps` consecutive launch_argmax calls on f32 logits (V,), the device
+    step counter starting at first_step and pos at 0.  ring=False passes a
+    null ring.  Returns dict(tokens (steps,) the token word after each launch,
+    pval (256,) f32 and pidx (256,) int32: the partials of the last launch,
+    part_guards (2, OP_GUARD) uint32, ring (first_step + steps,) uint32 or
+    None, ring_guards (OP_GUARD,) uint32 or None, pos, step).  Untouched
+    words hold OP_SENTINEL_BITS."""
+    logits = np.ascontiguousarray(logits, dtype=np.float32)
+    _, lp = _f32_shaped(logits, (logits.size,), "logits")
+    n = max(int(steps), 1)
+    G, NP = OP_GUARD, ARGMAX_PARTS
+    toks = np.empty(n, dtype=np.uint32)
+    pval = np.empty(NP + G, dtype=np.float32)
+    pidx = np.empty(NP + G, dtype=np.int32)
+    rbuf = np.empty(max(int(first_step), 0) + n + G, dtype=np.uint32)
+    ps = (ctypes.c_int * 2)()
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    _check(_lib.cake_hip_op_argmax(
+        logits.size, lp, temperature, seed, int(first_step), int(steps),
+        1 if ring else 0, int(advance_pos), toks.ctypes.data_as(u32p),
+        pval.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+        pidx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+        rbuf.ctypes.data_as(u32p) if ring else None, ps, device))
+    guards = np.stack([pval[NP:].view(np.uint32), pidx[NP:].view(np.uint32)])
+    return dict(tokens=toks, pval=pval[:NP], pidx=pidx[:NP],
+                part_guards=guards, ring=rbuf[:-G] if ring else None,
+                ring_guards=rbuf[-G:] if ring else None, pos=ps[0],
+                step=ps[1])
+
+
+def op_embed(table, ids, mode="rows", eps=1e-5, device=0):
+    """The embedding gathers on table (Vt, H) (f32, uploaded through the
+    f32 -> bf16 conversion).  mode "rows": launch_embed_rows on ids (S,);
+    "token": launch_embed_token on one id; "token_nscale": the same with the
+    fp8 norm chain's nscale.  Returns (out (S, H) f32, guards (OP_GUARD,),
+    nscale f32 (OP_SENTINEL unless requested), nscale guards (OP_GUARD,))."""
+    table = np.ascontiguousarray(table, dtype=np.float32)
+    if table.ndim != 2:
+        raise ValueError(f"table: shape {table.shape}, expected (Vt, H)")
+    Vt, H = table.shape
+    _, tp = _f32_shaped(table, (Vt, H), "table")
+    ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+    S = ids.size
+    out = np.empty(S * H + OP_GUARD, dtype=np.float32)
+    ns = np.empty(1 + OP_GUARD, dtype=np.float32)
+    fpp = ctypes.POINTER(ctypes.c_float)
+    _check(_lib.cake_hip_op_embed(
+        Vt, H, S, EMBED_MODES[mode], tp,
+        ids.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), eps,
+        out.ctypes.data_as(fpp), ns.ctypes.data_as(fpp), device))
+    return out[:S * H].reshape(S, H), out[S * H:], ns[0], ns[1:]
 
 
 def linear_dispatch(kind, n, K, M=1, fp8=False):

@@ -3143,6 +3143,119 @@ extern "C" int cake_hip_op_sample(int V, const float* logits,
   return 0;
 }
 
+// Test-only: `steps` consecutive launch_argmax calls (the greedy /
+// plain-temperature head of every decode step) on private buffers.  Every
+// word of the partials and of the ring starts as the bit pattern of
+// CAKE_HIP_OP_SENTINEL and both carry guards.
+extern "C" int cake_hip_op_argmax(int V, const float* logits,
+                                  float temperature, uint64_t seed,
+                                  int first_step, int steps, int use_ring,
+                                  int advance_pos, uint32_t* tokens_out,
+                                  float* pval_out, int32_t* pidx_out,
+                                  uint32_t* ring_out, int* pos_step_out,
+                                  int device) {
+  const char* who = "op_argmax";
+  const int NP = 256;  // launch_argmax's partition count
+  if (std::isnan(temperature))
+    return set_err(5, "%s: NaN temperature", who);
+  if (V < 1 || V > (1 << 24))
+    return set_err(5, "%s: V %d outside [1,%d]", who, V, 1 << 24);
+  if (steps < 1 || steps > 8192)
+    return set_err(5, "%s: steps %d outside [1,8192]", who, steps);
+  if (first_step < 0 || first_step > (1 << 20))
+    return set_err(5, "%s: first_step %d outside [0,%d]", who, first_step,
+                   1 << 20);
+  if (advance_pos != 0 && advance_pos != 1)
+    return set_err(5, "%s: advance_pos %d not 0|1", who, advance_pos);
+  if (!logits || !tokens_out || !pval_out || !pidx_out || !pos_step_out ||
+      (use_ring && !ring_out))
+    return set_err(5, "%s: null argument", who);
+  OpBufs b;
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreate(&b.s));
+  int r;
+  const size_t nring = (size_t)first_step + steps + OPG;
+  void *dl, *dtoks, *dmisc;
+  float *dpv, *dpi, *dring = nullptr;
+  if ((r = ob_upf32(b, logits, (size_t)V * 4, &dl))) return r;
+  if ((r = ob_sent32(b, NP + OPG, &dpv))) return r;
+  if ((r = ob_sent32(b, NP + OPG, &dpi))) return r;
+  if (use_ring && (r = ob_sent32(b, nring, &dring))) return r;
+  if ((r = ob_alloc(b, &dtoks, (size_t)steps * 4))) return r;
+  const int misc[3] = {0, 0, first_step};  // tok, pos, step
+  if ((r = ob_upf32(b, misc, sizeof misc, &dmisc))) return r;
+  u32* m = (u32*)dmisc;
+  const float inv_temp = temperature > 0.f ? 1.0f / temperature : 0.f;
+  for (int d = 0; d < steps; ++d) {
+    launch_argmax((const float*)dl, V, dpv, (int*)dpi, m, (int*)(m + 1),
+                  (u32*)dring, (int*)(m + 2), advance_pos, inv_temp, seed,
+                  b.s);
+    HIP_TRY(hipMemcpyAsync((u32*)dtoks + d, m, 4, hipMemcpyDeviceToDevice,
+                           b.s));
+  }
+  HIP_TRY(hipGetLastError());
+  int res[3];
+  HIP_TRY(hipMemcpyAsync(tokens_out, dtoks, (size_t)steps * 4,
+                         hipMemcpyDeviceToHost, b.s));
+  HIP_TRY(hipMemcpyAsync(pval_out, dpv, (NP + OPG) * 4,
+                         hipMemcpyDeviceToHost, b.s));
+  HIP_TRY(hipMemcpyAsync(pidx_out, dpi, (NP + OPG) * 4,
+                         hipMemcpyDeviceToHost, b.s));
+  if (use_ring)
+    HIP_TRY(hipMemcpyAsync(ring_out, dring, nring * 4, hipMemcpyDeviceToHost,
+                           b.s));
+  if ((r = ob_downf32(b, dmisc, sizeof res, res))) return r;
+  pos_step_out[0] = res[1];
+  pos_step_out[1] = res[2];
+  return 0;
+}
+
+// Test-only: the embedding gathers on a (Vt, H) table that crosses the
+// boundary as f32 and goes through the f32 -> bf16 upload every op entry
+// uses.  mode 0: launch_embed_rows on S ids; 1: launch_embed_token on one
+// id; 2: the same with the fp8 norm chain's nscale.
+extern "C" int cake_hip_op_embed(int Vt, int H, int S, int mode,
+                                 const float* table, const uint32_t* ids,
+                                 float eps, float* out, float* nscale_out,
+                                 int device) {
+  const char* who = "op_embed";
+  if (mode < 0 || mode > 2) return set_err(5, "%s: mode %d", who, mode);
+  // the hidden sizes engine create accepts
+  if (H < 8 || H > 16384 || H % 8 != 0)
+    return set_err(5, "%s: H %d must be a multiple of 8 in [8,16384]", who, H);
+  if (Vt < 1 || Vt > (1 << 20))
+    return set_err(5, "%s: Vt %d outside [1,%d]", who, Vt, 1 << 20);
+  if (S < 1 || S > 4096 || (mode != 0 && S != 1))
+    return set_err(5, "%s: S %d (rows: 1..4096, token: 1)", who, S);
+  if (!table || !ids || !out || !nscale_out)
+    return set_err(5, "%s: null argument", who);
+  for (int i = 0; i < S; ++i)
+    if (ids[i] >= (uint32_t)Vt)
+      return set_err(5, "%s: id %u outside the table (%d rows)", who, ids[i],
+                     Vt);
+  OpBufs b;
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreate(&b.s));
+  int r;
+  const size_t n = (size_t)S * H;
+  u16 *dt, *dout;
+  void* dids;
+  float* dns;
+  if ((r = ob_up16(b, table, (size_t)Vt * H, &dt))) return r;
+  if ((r = ob_upf32(b, ids, (size_t)S * 4, &dids))) return r;
+  if ((r = ob_sent16(b, n + OPG, &dout))) return r;
+  if ((r = ob_sent32(b, 1 + OPG, &dns))) return r;
+  if (mode == 0)
+    launch_embed_rows(dt, (const u32*)dids, dout, S, H, b.s);
+  else
+    launch_embed_token(dt, (const u32*)dids, dout, H, b.s,
+                       mode == 2 ? dns : nullptr, eps);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(nscale_out, dns, (1 + OPG) * 4,
+                         hipMemcpyDeviceToHost, b.s));
+  return ob_down16(b, dout, n + OPG, out);
+}
+
 extern "C" int cake_hip_set_stats(cake_engine* e, int enabled) {
   e->st.on = enabled != 0;
   return 0;

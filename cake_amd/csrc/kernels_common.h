@@ -54,6 +54,22 @@ __device__ inline void f8x16_decode(uint4v w, float* out) {
   }
 }
 
+// Gumbel noise of both samplers (k_argmax_part, k_sample_part) at vocabulary
+// index i; base = seed + GOLD * (draw + 1).  k = top 24 bits of the
+// splitmix64 hash, u = (min(k, 2^24 - 2) + 1) * 2^-24: u lies in
+// [2^-24, 1 - 2^-24], every value exact in f32, so -log(u) > 0 and the noise
+// is finite.  (Without the clamp k = 2^24 - 1 gives u == 1 and +inf noise:
+// that token would win whatever its logit.)
+__device__ inline float gumbel_noise(uint64_t base, int i) {
+  uint64_t z = base + 0xbf58476d1ce4e5b9ull * (uint64_t)(i + 1);
+  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+  z ^= z >> 31;
+  const u32 k = min((u32)(z >> 40), 0xfffffeu);
+  const float u = (float)(k + 1u) * 0x1p-24f;
+  return -__logf(-__logf(u));
+}
+
 __device__ inline float wave_sum(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, WAVE);

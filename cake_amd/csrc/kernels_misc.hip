@@ -218,7 +218,11 @@ __global__ void k_rope_simple(u16* __restrict__ x,
 // greedy ArgMax (temperature <= 0 semantics, text_model.rs:104).  The
 // uniform stream is a splitmix64 hash of (seed, step, index) — deterministic
 // and graph-replayable (step read from the device step counter); NOT
-// bit-matched to candle's StdRng (documented in DESIGN.md).
+// bit-matched to candle's StdRng (documented in DESIGN.md).  u stays inside
+// (0, 1): gumbel_noise, kernels_common.h.
+// Contract: the token is the first index whose value equals the maximum
+// over the non-NaN entries (NaN never compares greater); when no entry is
+// greater than -inf the token is 0.  It is always < n.
 __global__ void k_argmax_part(const float* __restrict__ logits, int n,
                               float* __restrict__ pval, int* __restrict__ pidx,
                               int nparts, float inv_temp, uint64_t seed,
@@ -232,15 +236,7 @@ __global__ void k_argmax_part(const float* __restrict__ logits, int n,
   int bidx = 0x7fffffff;
   for (int i = start + (int)threadIdx.x; i < end; i += blockDim.x) {
     float v = logits[i];
-    if (inv_temp > 0.f) {
-      uint64_t z = base + 0xbf58476d1ce4e5b9ull * (uint64_t)(i + 1);
-      z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-      z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-      z ^= z >> 31;
-      // u in (0, 1): top 24 bits, +1 to avoid exactly 0
-      float u = ((float)(z >> 40) + 1.0f) * (1.0f / 16777217.0f);
-      v = v * inv_temp + (-__logf(-__logf(u)));
-    }
+    if (inv_temp > 0.f) v = v * inv_temp + gumbel_noise(base, i);
     if (v > best || (v == best && i < bidx)) { best = v; bidx = i; }
   }
   // wave+block reduce keeping first index on ties
@@ -295,9 +291,12 @@ __global__ void k_argmax_fin(const float* __restrict__ pval,
     __syncthreads();
   }
   if (threadIdx.x == 0) {
-    *tok = (u32)si[0];
+    // nothing compared greater than -inf (all -inf and/or NaN): token 0, so
+    // the "no index" value of an all-NaN span never leaves as a token
+    const u32 t = sv[0] > -INFINITY ? (u32)si[0] : 0u;
+    *tok = t;
     if (ring) {
-      ring[*step] = (u32)si[0];
+      ring[*step] = t;
       *step += 1;
     }
     if (advance_pos) *pos += 1;

@@ -278,14 +278,7 @@ __global__ void k_sample_part(int V, int nb, SampleWs b, int p_last,
   for (int i = start + tid; i < end; i += 256) {
     float v = b.work[i];
     if (f2key(v) < tkey) continue;
-    if (inv_temp > 0.f) {
-      uint64_t z = base + 0xbf58476d1ce4e5b9ull * (uint64_t)(i + 1);
-      z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-      z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-      z ^= z >> 31;
-      float u = ((float)(z >> 40) + 1.0f) * (1.0f / 16777217.0f);
-      v = v * inv_temp + (-__logf(-__logf(u)));
-    }
+    if (inv_temp > 0.f) v = v * inv_temp + gumbel_noise(base, i);
     if (v > best || (v == best && i < bidx)) { best = v; bidx = i; }
   }
   __shared__ float sv[256];
@@ -333,7 +326,8 @@ __global__ void k_sample_fin(int V, int nb, SampleWs b, int sel_on,
     __syncthreads();
   }
   if (tid == 0) {
-    const u32 t = (u32)si[0];
+    // as k_argmax_fin: nothing above -inf (all -inf and/or NaN) is token 0
+    const u32 t = sv[0] > -INFINITY ? (u32)si[0] : 0u;
     *tok = t;
     if (ring) {
       ring[*step] = t;

@@ -388,6 +388,34 @@ int cake_hip_op_sample(int V, const float *logits, float temperature,
                        uint64_t seed, int first_draw, int draws,
                        uint32_t *tokens_out, int *kept_out, float *thr_out,
                        int device);
+/* Test-only: `steps` (1..8192) consecutive launch_argmax calls on the same
+ * f32 logits (V <= 2^24), private buffers and stream.  temperature <= 0 is
+ * the greedy argmax, > 0 the seeded Gumbel-argmax.  The device step counter
+ * starts at first_step (<= 2^20), pos at 0.  use_ring 0 passes a null ring
+ * (the step counter then stays put).  Contract of the token: the first index
+ * whose value equals the maximum over the non-NaN entries; 0 when no entry
+ * is greater than -inf; always < V.
+ * tokens_out[steps]: the token word after each launch.  pval_out / pidx_out
+ * (256 + CAKE_HIP_OP_GUARD each): the partials of the LAST launch.  ring_out
+ * (first_step + steps + CAKE_HIP_OP_GUARD words, ignored without use_ring):
+ * the whole ring.  Partials, ring and their guards start as the bit pattern
+ * of CAKE_HIP_OP_SENTINEL.  pos_step_out = {pos, step} after the last launch.
+ * Arguments are validated before any device call (error 5). */
+int cake_hip_op_argmax(int V, const float *logits, float temperature,
+                       uint64_t seed, int first_step, int steps, int use_ring,
+                       int advance_pos, uint32_t *tokens_out, float *pval_out,
+                       int32_t *pidx_out, uint32_t *ring_out,
+                       int *pos_step_out, int device);
+/* Test-only: the embedding gathers on table (Vt, H), which crosses as f32 and
+ * is uploaded through the f32 -> bf16 conversion.  mode 0: launch_embed_rows
+ * on S ids; 1: launch_embed_token on one id; 2: the same, also producing the
+ * fp8 norm chain's nscale = 1/sqrt(mean(x^2) + eps).  H % 8 == 0,
+ * 8 <= H <= 16384 (what engine create accepts); ids < Vt.  out is
+ * (S*H + CAKE_HIP_OP_GUARD); nscale_out is (1 + CAKE_HIP_OP_GUARD) and keeps
+ * the sentinel unless mode 2. */
+int cake_hip_op_embed(int Vt, int H, int S, int mode, const float *table,
+                      const uint32_t *ids, float eps, float *out,
+                      float *nscale_out, int device);
 int cake_hip_stats_reset(cake_engine *e);
 int cake_hip_set_stats(cake_engine *e, int enabled);
 

@@ -22,17 +22,35 @@ _M1 = np.uint64(0xbf58476d1ce4e5b9)
 _M2 = np.uint64(0x94d049bb133111eb)
 
 
-def uniform_stream(seed, draw, V):
-    """u_i in (0,1) for i < V at draw index `draw`: splitmix64 of
-    seed + GOLD * (draw + 1) + M1 * (i + 1), top 24 bits, as float32."""
+K_MAX = (1 << 24) - 2        # the clamp of the top 24 hash bits
+
+
+def u_of_hash(z):
+    """The contract: k = top 24 bits of the hash,
+    u = (min(k, 2^24 - 2) + 1) * 2^-24, worked from the integer k in float64.
+    u lies in [2^-24, 1 - 2^-24]; every value is exact in float32."""
+    k = np.minimum((z >> np.uint64(40)).astype(np.int64), K_MAX)
+    u = (k + 1).astype(np.float64) * 2.0 ** -24
+    assert ((u > 0) & (u < 1)).all()
+    return u
+
+
+def hash64(base, i1):
+    """splitmix64 finaliser of base + M1 * i1 (uint64 arrays, wrapping)."""
     with np.errstate(over="ignore"):
-        base = np.uint64(seed) + _GOLD * np.uint64(draw + 1)
-        z = base + _M1 * np.arange(1, V + 1, dtype=np.uint64)
+        z = base + _M1 * i1
         z = (z ^ (z >> np.uint64(30))) * _M1
         z = (z ^ (z >> np.uint64(27))) * _M2
-        z = z ^ (z >> np.uint64(31))
-    top = (z >> np.uint64(40)).astype(np.float32)
-    return (top + np.float32(1.0)) * (np.float32(1.0) / np.float32(16777217.0))
+        return z ^ (z >> np.uint64(31))
+
+
+def uniform_stream(seed, draw, V):
+    """u_i in (0,1) for i < V at draw index `draw`: splitmix64 of
+    seed + GOLD * (draw + 1) + M1 * (i + 1), top 24 bits clamped to 2^24 - 2,
+    plus one, times 2^-24 (float64 holding f32-exact values)."""
+    with np.errstate(over="ignore"):
+        base = np.uint64(seed) + _GOLD * np.uint64(draw + 1)
+    return u_of_hash(hash64(base, np.arange(1, V + 1, dtype=np.uint64)))
 
 
 def uniform_at(seed, draws, ids):
@@ -41,13 +59,8 @@ def uniform_at(seed, draws, ids):
     d = np.asarray(draws, dtype=np.uint64)[:, None]
     i = np.asarray(ids, dtype=np.uint64)[None, :]
     with np.errstate(over="ignore"):
-        z = (np.uint64(seed) + _GOLD * (d + np.uint64(1)) +
-             _M1 * (i + np.uint64(1)))
-        z = (z ^ (z >> np.uint64(30))) * _M1
-        z = (z ^ (z >> np.uint64(27))) * _M2
-        z = z ^ (z >> np.uint64(31))
-    top = (z >> np.uint64(40)).astype(np.float32)
-    return (top + np.float32(1.0)) * (np.float32(1.0) / np.float32(16777217.0))
+        base = np.uint64(seed) + _GOLD * (d + np.uint64(1))
+    return u_of_hash(hash64(base, i + np.uint64(1)))
 
 
 def draws_on_support(lp, ids, temperature, seed, first, n):

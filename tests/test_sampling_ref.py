@@ -146,15 +146,34 @@ def test_uniform_stream_restatement():
         z = ((z ^ (z >> 30)) * 0xbf58476d1ce4e5b9) & M
         z = ((z ^ (z >> 27)) * 0x94d049bb133111eb) & M
         z ^= z >> 31
-        return (np.float32(z >> 40) + np.float32(1)) * (
-            np.float32(1) / np.float32(16777217.0))
+        # the contract, in integers: (min(k, 2^24 - 2) + 1) / 2^24
+        return (min(z >> 40, (1 << 24) - 2) + 1) / (1 << 24)
 
     u = sr.uniform_stream(seed, draw, 64)
     assert u[i] == u_of(seed, draw, i)
     assert (u > 0).all() and (u < 1).all()
+    assert np.array_equal(u.astype(np.float32).astype(np.float64), u)
     sub = sr.uniform_at(seed, [draw, draw + 1], [3, i])
     assert sub[0, 1] == u[i] and sub[0, 0] == u[3]
     assert sub[1, 0] == u_of(seed, draw + 1, 3)
+
+
+def test_uniform_stream_stays_inside_the_open_interval_at_the_extremes():
+    """The hash bits k = 2^24 - 1 (where the f32 expression ((float)k + 1) *
+    (1 / 16777217.0f) gave exactly 1, hence +inf noise) and k = 0."""
+    from tests import head_cases as hc
+    for k, (seed, draw, i) in hc.extreme_rows():
+        u = sr.uniform_stream(seed, draw, hc.EXTREMES_V)
+        assert (u > 0).all() and (u < 1).all()
+        assert u[i] == u_of_k(k) == sr.uniform_at(seed, [draw], [i])[0, 0]
+        assert np.isfinite(sr.gumbel(seed, draw, hc.EXTREMES_V)).all()
+    seed, draw, i = hc.POISON_PRODUCT
+    u = sr.uniform_stream(seed, draw, hc.PRODUCT_V)
+    assert u[i] == 1 - 2.0 ** -24 and u.max() == u[i] and u.min() > 0
+
+
+def u_of_k(k):
+    return (min(k, (1 << 24) - 2) + 1) / (1 << 24)
 
 
 def test_op_sample_validates_before_any_device_call():
