@@ -63,6 +63,8 @@ def _load_lib():
     f = ctypes.c_float
     lib.cake_hip_op_kv_store.argtypes = [c, c, c, c, c, c, c, fp, fp, fp, fp,
                                          fp, f, fp, fp, fp, fp, c]
+    lib.cake_hip_op_kv_store_bias.argtypes = [c] * 7 + [fp] * 5 + [f] + \
+        [fp] * 5 + [c]
     lib.cake_hip_op_attn_prefill.argtypes = [c] * 11 + [fp] * 5 + [c]
     lib.cake_hip_op_attn_decode.argtypes = [c] * 8 + [fp] * 4 + [c]
     lib.cake_hip_attn_dispatch.argtypes = [c, c, c, c, ctypes.POINTER(c)]
@@ -76,6 +78,8 @@ def _load_lib():
                                             f, fp, fp, c]
     lib.cake_hip_op_gemv_qkv_rope.argtypes = [c] * 6 + [fp, fp, f] + \
         [fp] * 7 + [c]
+    lib.cake_hip_op_gemv_qkv_rope_bias.argtypes = [c] * 6 + [fp, fp, f] + \
+        [fp] * 8 + [c]
     lib.cake_hip_op_gemm.argtypes = [c] * 6 + [fp, fp, fp, fp,
                                                ctypes.POINTER(c), c]
     lib.cake_hip_op_dequant_fp8.argtypes = [c, c, u8p, fp, fp, c]
@@ -208,6 +212,22 @@ def op_kv_store(qkv, cos, sin, kc, vc, vtc, pos0, nh, nkv, q_norm=None,
     at positions pos0.. (decode=True: the one-row decode kernel).  kc/vc
     (nkv, max_seq, hd) and vtc (nkv, hd, max_seq) are the PRIOR cache images;
     returns (roped q (S, nh, hd), kc, vc, vtc) after the store."""
+    return _op_kv_store(False, None, qkv, cos, sin, kc, vc, vtc, pos0, nh,
+                        nkv, q_norm, k_norm, eps, decode, device)
+
+
+def op_kv_store_bias(qkv, bias, cos, sin, kc, vc, vtc, pos0, nh, nkv,
+                     q_norm=None, k_norm=None, eps=1e-6, decode=False,
+                     device=0):
+    """op_kv_store through cake_hip_op_kv_store_bias: bias is the fused
+    q|k|v projection bias row ((nh+2*nkv)*hd f32, qwen2), added to every raw
+    row in f32 ahead of the rotation / the V store, or None."""
+    return _op_kv_store(True, bias, qkv, cos, sin, kc, vc, vtc, pos0, nh, nkv,
+                        q_norm, k_norm, eps, decode, device)
+
+
+def _op_kv_store(bias_entry, bias, qkv, cos, sin, kc, vc, vtc, pos0, nh, nkv,
+                 q_norm, k_norm, eps, decode, device):
     kc = np.array(kc, dtype=np.float32, order="C")
     nkv_, max_seq, hd = kc.shape if kc.ndim == 3 else (0, 0, 0)
     qkv = np.ascontiguousarray(qkv, dtype=np.float32)
@@ -226,10 +246,15 @@ def op_kv_store(qkv, cos, sin, kc, vc, vtc, pos0, nh, nkv, q_norm=None,
     if k_norm is not None:
         kn, knp = _f32_shaped(k_norm, (hd,), "k_norm")
     q_out = np.empty((S, nh, hd), dtype=np.float32)
-    _check(_lib.cake_hip_op_kv_store(
-        S, pos0, 1 if decode else 0, nh, nkv, hd, max_seq, qp, cp, sp, qnp,
-        knp, ctypes.c_float(eps), kp, vp, vtp,
-        q_out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), device))
+    head = (S, pos0, 1 if decode else 0, nh, nkv, hd, max_seq, qp, cp, sp,
+            qnp, knp, ctypes.c_float(eps))
+    tail = (kp, vp, vtp,
+            q_out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), device)
+    if bias_entry:
+        _b, bp = _opt_f32(bias, ((nh + 2 * nkv) * hd,), "bias")
+        _check(_lib.cake_hip_op_kv_store_bias(*head, bp, *tail))
+    else:
+        _check(_lib.cake_hip_op_kv_store(*head, *tail))
     return q_out, kc, vc, vtc
 
 
@@ -433,6 +458,22 @@ def op_gemv_qkv_rope(x, nw, w, cos, sin, kc, vc, vtc, pos, nh, nkv,
     (nkv, max_seq, hd), vtc (nkv, hd, max_seq) are the PRIOR images.  Returns
     (roped q (nh, hd), rest of the activation row incl. guards, kc, vc,
     vtc)."""
+    return _op_gemv_qkv_rope(False, None, x, nw, w, cos, sin, kc, vc, vtc,
+                             pos, nh, nkv, eps, device)
+
+
+def op_gemv_qkv_rope_bias(x, nw, w, bias, cos, sin, kc, vc, vtc, pos, nh, nkv,
+                          eps=1e-5, device=0):
+    """op_gemv_qkv_rope through cake_hip_op_gemv_qkv_rope_bias: bias is the
+    fused q|k|v projection bias row ((nh+2*nkv)*hd f32), added to the f32
+    sums ahead of the rotation / the V store (the biased kernel), or None (the
+    unbiased one)."""
+    return _op_gemv_qkv_rope(True, bias, x, nw, w, cos, sin, kc, vc, vtc, pos,
+                             nh, nkv, eps, device)
+
+
+def _op_gemv_qkv_rope(bias_entry, bias, x, nw, w, cos, sin, kc, vc, vtc, pos,
+                      nh, nkv, eps, device):
     kc = np.array(kc, dtype=np.float32, order="C")
     nkv_, max_seq, hd = kc.shape
     x = np.ascontiguousarray(x, dtype=np.float32)
@@ -449,9 +490,14 @@ def op_gemv_qkv_rope(x, nw, w, cos, sin, kc, vc, vtc, pos, nh, nkv,
     vtc, vtp = _f32_shaped(np.array(vtc, dtype=np.float32, order="C"),
                            (nkv, hd, max_seq), "vtc")
     out = np.empty(Nq + OP_GUARD, dtype=np.float32)
-    _check(_lib.cake_hip_op_gemv_qkv_rope(
-        nh, nkv, hd, max_seq, pos, K, xp, nwp, eps, wp, cp, sp, kp, vp, vtp,
-        out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), device))
+    head = (nh, nkv, hd, max_seq, pos, K, xp, nwp, eps, wp, cp, sp)
+    tail = (kp, vp, vtp, out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+            device)
+    if bias_entry:
+        _b, bp = _opt_f32(bias, (Nq,), "bias")
+        _check(_lib.cake_hip_op_gemv_qkv_rope_bias(*head, bp, *tail))
+    else:
+        _check(_lib.cake_hip_op_gemv_qkv_rope(*head, *tail))
     return out[:nh * hd].reshape(nh, hd), out[nh * hd:], kc, vc, vtc
 
 

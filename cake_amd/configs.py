@@ -56,6 +56,27 @@ LLAMA3_8B_GPTQ = dict(LLAMA3_8B,
     quantization_config=dict(quant_method="gptq", bits=4, group_size=128,
                              desc_act=False, sym=True))
 
+# Qwen2.5 (qwen2/): the llama-shaped Transformer plus an additive bias on the
+# q, k and v projections (qwen2/config.rs:84).  The official GPTQ-Int4
+# checkpoints are group 128 without act-order and keep F16 biases.
+QWEN2_5_0_5B = dict(
+    model_type="qwen2", hidden_size=896, intermediate_size=4864,
+    vocab_size=151936, num_hidden_layers=24, num_attention_heads=14,
+    num_key_value_heads=2, head_dim=64, rms_norm_eps=1e-6,
+    rope_theta=1000000.0, max_position_embeddings=32768,
+    tie_word_embeddings=True)
+
+QWEN2_5_7B = dict(
+    model_type="qwen2", hidden_size=3584, intermediate_size=18944,
+    vocab_size=152064, num_hidden_layers=28, num_attention_heads=28,
+    num_key_value_heads=4, head_dim=128, rms_norm_eps=1e-6,
+    rope_theta=1000000.0, max_position_embeddings=32768,
+    tie_word_embeddings=False)
+
+QWEN2_5_7B_GPTQ = dict(QWEN2_5_7B,
+    quantization_config=dict(quant_method="gptq", bits=4, group_size=128,
+                             desc_act=False, sym=True))
+
 MODELS = {
     "llama3-8b": LLAMA3_8B,
     "llama3-70b": LLAMA3_70B,
@@ -72,24 +93,43 @@ QUANT_MODELS = {
 }
 
 
+# the qwen2 family (q/k/v projection bias), beside the two tables above
+QWEN2_MODELS = {
+    "qwen2.5-0.5b": QWEN2_5_0_5B,
+    "qwen2.5-7b": QWEN2_5_7B,
+    "qwen2.5-7b-gptq": QWEN2_5_7B_GPTQ,
+}
+
+
+def find_model(name: str) -> dict:
+    """The config called `name` in MODELS, QUANT_MODELS or QWEN2_MODELS."""
+    for table in (MODELS, QUANT_MODELS, QWEN2_MODELS):
+        if name in table:
+            return table[name]
+    raise KeyError(name)
+
+
 def weight_bytes(cfg: dict, lo=0, hi=None, embed=True, head=True) -> int:
     """Bytes of weights resident in HBM for this config: bf16, or for a gptq
     config the device 4-bit layout (packed nibbles + an f32 {scale, zero
-    term} pair per row and group) with 16-bit embedding, head and norms."""
+    term} pair per row and group) with 16-bit embedding, head and norms.  A
+    qwen2 config adds its fused f32 q|k|v bias row per layer."""
     q = cfg.get("quantization_config") or {}
-    if q.get("quant_method") != "gptq":
-        return weight_bytes_bf16(cfg, lo, hi, embed, head)
     H, I, V = cfg["hidden_size"], cfg["intermediate_size"], cfg["vocab_size"]
     nh, nkv = cfg["num_attention_heads"], cfg["num_key_value_heads"]
     hd = cfg.get("head_dim") or H // nh
     L = (hi if hi is not None else cfg["num_hidden_layers"]) - lo
+    bias = L * (nh + 2 * nkv) * hd * 4 if cfg.get("model_type") == "qwen2" \
+        else 0
+    if q.get("quant_method") != "gptq":
+        return weight_bytes_bf16(cfg, lo, hi, embed, head) + bias
     g = q.get("group_size", 128)
 
     def w4(n, k):
         return n * k // 2 + n * (k // (k if g == -1 else g)) * 8
     per_layer = (w4((nh + 2 * nkv) * hd, H) + w4(H, nh * hd) +
                  w4(2 * I, H) + w4(H, I) + 2 * H * 2)
-    total = L * per_layer
+    total = L * per_layer + bias
     if embed:
         total += V * H * 2
     if head:

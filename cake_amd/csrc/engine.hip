@@ -85,6 +85,8 @@ struct ModelConfig {
   }
   float rms_eps = 1e-5f, rope_theta = 10000.f;
   bool tied = false, qk_norm = false;
+  bool qkv_bias = false;  // qwen2: q/k/v projections carry an additive bias
+                          // (qwen2/config.rs:84, attention.rs:95-104)
   bool fp8 = false;  // quantization_config.quant_method == "fp8" (fp8.rs:20-40)
   bool w4 = false;   // quant_method == "gptq", bits 4 (gptq.rs:69-86)
   int group = 128;   // gptq group_size; -1 = one group per row
@@ -124,8 +126,22 @@ static int parse_config(const char* json, ModelConfig* c) {
   if (auto p = v->get("rms_norm_eps")) c->rms_eps = (float)p->num;
   if (auto p = v->get("rope_theta")) c->rope_theta = (float)p->num;
   if (auto p = v->get("tie_word_embeddings")) c->tied = p->bool_or(false);
-  if (auto p = v->get("model_type"))
+  if (auto p = v->get("model_type")) {
     c->qk_norm = p->str.find("qwen3") != std::string::npos;
+    c->qkv_bias = p->str == "qwen2";
+    // qwen2's own default (qwen2/config.rs:7-9)
+    if (c->qkv_bias && !v->get("rope_theta")) c->rope_theta = 1e6f;
+  }
+  // A bias this engine would silently drop is refused: only qwen2's q/k/v
+  // bias is implemented (no o-proj or MLP bias, none under QK-norm).
+  for (const char* k : {"attention_bias", "mlp_bias"})
+    if (auto p = v->get(k))
+      if (p->bool_or(false) && !c->qkv_bias)
+        return set_err(5, "config.json: %s true is not supported (only the "
+                          "q/k/v bias of model_type qwen2 is)", k);
+  if (c->qkv_bias && c->qk_norm)
+    return set_err(5, "config.json: q/k/v bias together with QK-norm is not "
+                      "supported");
   // sliding window (mistral-style; qwen gates it behind use_sliding_window
   // and applies it only from max_window_layers up; HF "layer_types" has
   // the same full-then-sliding shape for these families)
@@ -280,6 +296,9 @@ struct LayerDev {
   u16 *rms1 = nullptr, *rms2 = nullptr;
   u16 *wqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wdown = nullptr;
   u16 *qnorm = nullptr, *knorm = nullptr;
+  // qwen2: fused q|k|v projection bias, (Nq) f32 in wqkv's row order (f32 so
+  // that an F16 bias of a GPTQ checkpoint stays exact); null otherwise
+  float* bqkv = nullptr;
   u16 *kc = nullptr, *vc = nullptr;  // (nkv, max_seq, hd) each
   u16 *vtc = nullptr;                // V transposed: (nkv, hd, max_seq)
   // fp8 weights (e4m3fn bytes + blockwise 128x128 scale_inv, fp8.rs:42-64)
@@ -455,7 +474,8 @@ static void stats_flush(cake_engine* e) {
 
 // Full-rotation models without qk-norm and without fp8/4-bit weights take the
 // fused rms_norm -> qkv GEMV -> rope -> KV-store kernel (the QK-norm rows
-// exist exactly when c.qk_norm).  Shared with cake_hip_decode_dispatch.
+// exist exactly when c.qk_norm; qwen2 takes its biased twin).  Shared with
+// cake_hip_decode_dispatch.
 // algorithmic bytes of one packed 4-bit tensor: nibbles + {s, -(z+1)s} pairs
 static double w4_bytes(double N, double K, double g) {
   return N * K * 0.5 + N * (K / g) * 8.0;
@@ -484,7 +504,7 @@ static void enqueue_layer_decode(cake_engine* e, LayerDev& l,
     StatScope ss(e, "gemv_qkv", wb + 2.0 * H * 2 + Nq * 2, 2.0 * Nq * H);
     launch_gemv_qkv_rope(l.wqkv, e->x, e->qkv, l.rms1, c.rms_eps, l.kc,
                          l.vc, l.vtc, e->cos_t, e->sin_t, e->dev_pos, c.nh,
-                         c.nkv, hd, e->max_seq, H, e->stream);
+                         c.nkv, hd, e->max_seq, H, e->stream, l.bqkv);
   } else if (c.w4) {  // split norm -> 4-bit GEMV -> rope + KV store
     {
       StatScope ss(e, "rmsnorm", 2.0 * H * 2, 0);
@@ -499,7 +519,7 @@ static void enqueue_layer_decode(cake_engine* e, LayerDev& l,
     StatScope ss(e, "rope_store", 0, 0);
     launch_rope_store_decode(e->qkv, l.kc, l.vc, l.vtc, e->cos_t, e->sin_t,
                              e->dev_pos, c.nh, c.nkv, hd, hd, e->max_seq,
-                             l.qnorm, l.knorm, c.rms_eps, e->stream);
+                             l.qnorm, l.knorm, c.rms_eps, e->stream, l.bqkv);
   } else {
     {  // rms_1 fused into the qkv projection (GEMV, x kept in registers)
       double wb = (double)Nq * H * (c.fp8 ? 1 : 2);
@@ -528,11 +548,13 @@ static void enqueue_layer_decode(cake_engine* e, LayerDev& l,
         launch_gemv(l.wqkv, e->x, e->qkv, nullptr, l.rms1, c.rms_eps, Nq, H,
                     0, e->stream);
     }
-    {  // [Qwen3 QK-norm, attention.rs:202-215, fused +] rope + KV store
+    {  // [Qwen3 QK-norm, attention.rs:202-215 | qwen2 bias, fused +] rope +
+       // KV store
       StatScope ss(e, "rope_store", (double)Nq * hd * 0, 0);
       launch_rope_store_decode(e->qkv, l.kc, l.vc, l.vtc, e->cos_t, e->sin_t,
                                e->dev_pos, c.nh, c.nkv, hd, hd, e->max_seq,
-                               l.qnorm, l.knorm, c.rms_eps, e->stream);
+                               l.qnorm, l.knorm, c.rms_eps, e->stream,
+                               l.bqkv);
     }
   }
   {  // decode attention over the cache (single launch, split-KV combine)
@@ -664,11 +686,11 @@ static void enqueue_layer_prefill(cake_engine* e, LayerDev& l, int S,
                  2.0 * S * Nq * H);
     launch_gemm(e->xn, wqkv, e->qkv, nullptr, S, Nq, H, 0, e->stream);
   }
-  {  // [fused QK-norm +] rope + KV store for all S positions
+  {  // [fused QK-norm | qkv bias +] rope + KV store for all S positions
     StatScope ss(e, "rope_store_pf", 0, 0);
     launch_rope_store_prefill(e->qkv, l.kc, l.vc, l.vtc, e->cos_t, e->sin_t,
                               pos0, S, c.nh, c.nkv, hd, hd, e->max_seq, Nq,
-                              l.qnorm, l.knorm, c.rms_eps, e->stream);
+                              l.qnorm, l.knorm, c.rms_eps, e->stream, l.bqkv);
   }
   {
     double n_avg = pos0 + (S + 1) * 0.5;
@@ -878,6 +900,7 @@ extern "C" int cake_hip_engine_create(const char* config_json, int layer_lo,
       ALLOC(l.qnorm, u16, hd);
       ALLOC(l.knorm, u16, hd);
     }
+    if (c.qkv_bias) ALLOC(l.bqkv, float, Nq);
     ALLOC(l.kc, u16, (size_t)c.nkv * max_seq * hd);
     ALLOC(l.vc, u16, (size_t)c.nkv * max_seq * hd);
     ALLOC(l.vtc, u16, (size_t)c.nkv * hd * max_seq);
@@ -1003,6 +1026,7 @@ extern "C" void cake_hip_engine_free(cake_engine* e) {
       hipFree(l.zqkv); hipFree(l.zo); hipFree(l.zgu); hipFree(l.zdown);
     }
     if (l.qnorm) { hipFree(l.qnorm); hipFree(l.knorm); }
+    if (l.bqkv) hipFree(l.bqkv);
   }
   if (e->embed) hipFree(e->embed);
   if (e->lm_head && e->lm_head != e->embed) hipFree(e->lm_head);
@@ -1143,6 +1167,36 @@ static int upload_weight(cake_engine* e, u16* dst, const char* filebase,
   } else {
     return set_err(5, "unsupported safetensors dtype %s", t.dtype.c_str());
   }
+  return 0;
+}
+
+// one projection's bias vector -> f32 (every source dtype widens exactly)
+static int upload_bias(cake_engine* e, float* dst, const char* filebase,
+                       const StTensor& t, const std::string& name,
+                       size_t expect) {
+  if (t.shape.size() != 1 || (size_t)t.shape[0] != expect) {
+    std::string got;
+    for (long d : t.shape) got += (got.empty() ? "" : ", ") + std::to_string(d);
+    return set_err(5, "%s: shape (%s), expected (%zu)", name.c_str(),
+                   got.c_str(), expect);
+  }
+  const char* src = filebase + t.off0;
+  std::vector<float> tmp(expect);
+  if (t.dtype == "F32") {
+    memcpy(tmp.data(), src, expect * 4);
+  } else if (t.dtype == "F16") {
+    for (size_t i = 0; i < expect; ++i) tmp[i] = f16_at(src, i);
+  } else if (t.dtype == "BF16") {
+    for (size_t i = 0; i < expect; ++i) {
+      u16 h;
+      memcpy(&h, src + i * 2, 2);
+      tmp[i] = b2f_host(h);
+    }
+  } else {
+    return set_err(5, "%s: dtype %s, expected F32, F16 or BF16", name.c_str(),
+                   t.dtype.c_str());
+  }
+  HIP_TRY(hipMemcpy(dst, tmp.data(), expect * 4, hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -1399,8 +1453,8 @@ static int load_safetensors_file(cake_engine* e, const char* path) {
       LOADW(pre + "mlp.down_proj.weight_scale_inv", upload_scale(e, l.sdown, base, t, Hb * Ib));
     } else if (c.w4) {
       // gptq: qweight/qzeros/scales per projection, repacked out-major at
-      // the projection's row offset of the fused tensor (g_idx and bias are
-      // ignored, as gptq.rs does)
+      // the projection's row offset of the fused tensor (g_idx is ignored,
+      // as gptq.rs does; so is every bias but qwen2's q/k/v, loaded below)
       const size_t gH = c.grp((int)H), gS = c.grp((int)Sq), gI = c.grp((int)I);
       if ((r = load_w4(pre + "self_attn.q_proj", l.wqkv4, l.zqkv, 0, Sq, H, gH))) return r;
       if ((r = load_w4(pre + "self_attn.k_proj", l.wqkv4, l.zqkv, Sq, Skv, H, gH))) return r;
@@ -1419,6 +1473,13 @@ static int load_safetensors_file(cake_engine* e, const char* path) {
     LOADW(pre + "mlp.gate_proj.weight", upload_weight(e, l.wgu, base, t, I * H));
     LOADW(pre + "mlp.up_proj.weight", upload_weight(e, l.wgu + I * H, base, t, I * H));
     LOADW(pre + "mlp.down_proj.weight", upload_weight(e, l.wdown, base, t, H * I));
+    }
+    if (c.qkv_bias) {
+      // qwen2, every weight format alike: required F32/F16/BF16 vectors at
+      // the projection's row offset of the fused bias (attention.rs:95-104)
+      LOADW(pre + "self_attn.q_proj.bias", upload_bias(e, l.bqkv, base, t, pre + "self_attn.q_proj.bias", Sq));
+      LOADW(pre + "self_attn.k_proj.bias", upload_bias(e, l.bqkv + Sq, base, t, pre + "self_attn.k_proj.bias", Skv));
+      LOADW(pre + "self_attn.v_proj.bias", upload_bias(e, l.bqkv + Sq + Skv, base, t, pre + "self_attn.v_proj.bias", Skv));
     }
     if (c.qk_norm) {
       LOADW(pre + "self_attn.q_norm.weight", upload_weight(e, l.qnorm, base, t, hd));
@@ -1512,6 +1573,22 @@ extern "C" int cake_hip_init_random(cake_engine* e, uint64_t seed,
     if (l.qnorm) {
       launch_fill_const(l.qnorm, hd, 1.0f, e->stream);
       launch_fill_const(l.knorm, hd, 1.0f, e->stream);
+    }
+    if (l.bqkv) {
+      // slot 4 of the layer: q and k rows ~uniform(+-3) (real qwen2 q/k
+      // biases are large), v rows ~uniform(+-0.25); splitmix64 of the index
+      const uint64_t bs = seed + 0x1000193u * (base + 4);
+      hscales.resize(Sq + 2 * Skv);
+      for (size_t i = 0; i < hscales.size(); ++i) {
+        uint64_t z = bs + 0x9e3779b97f4a7c15ull * (uint64_t)(i + 1);
+        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+        z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+        z ^= z >> 31;
+        const float u = (float)(z >> 40) * 0x1p-23f - 1.f;  // [-1, 1)
+        hscales[i] = u * (i < Sq + Skv ? 3.f : 0.25f);
+      }
+      hipMemcpy(l.bqkv, hscales.data(), hscales.size() * 4,
+                hipMemcpyHostToDevice);
     }
   }
   HIP_TRY(hipStreamSynchronize(e->stream));
@@ -2156,14 +2233,14 @@ static int attn_geom_err(const char* who, int nh, int nkv, int hd,
   return 0;
 }
 
-extern "C" int cake_hip_op_kv_store(int S, int pos0, int decode, int nh,
-                                    int nkv, int hd, int max_seq,
-                                    const float* qkv, const float* cosv,
-                                    const float* sinv, const float* q_norm,
-                                    const float* k_norm, float eps, float* kc,
-                                    float* vc, float* vtc, float* q_out,
-                                    int device) {
-  const char* who = "op_kv_store";
+// shared body of cake_hip_op_kv_store[_bias]; bias may be null
+static int op_kv_store_impl(const char* who, int S, int pos0, int decode,
+                            int nh, int nkv, int hd, int max_seq,
+                            const float* qkv, const float* cosv,
+                            const float* sinv, const float* q_norm,
+                            const float* k_norm, float eps,
+                            const float* bias, float* kc, float* vc,
+                            float* vtc, float* q_out, int device) {
   int r = attn_geom_err(who, nh, nkv, hd, max_seq);
   if (r) return r;
   if (S < 1 || pos0 < 0 || pos0 + S > max_seq)
@@ -2173,6 +2250,9 @@ extern "C" int cake_hip_op_kv_store(int S, int pos0, int decode, int nh,
     return set_err(5, "%s: the decode store takes one row (got %d)", who, S);
   if ((q_norm == nullptr) != (k_norm == nullptr))
     return set_err(5, "%s: q_norm and k_norm go together", who);
+  if (bias && q_norm)
+    return set_err(5, "%s: a bias together with QK-norm is not supported",
+                   who);
   OpBufs b;
   HIP_TRY(hipSetDevice(device));
   HIP_TRY(hipStreamCreate(&b.s));
@@ -2180,8 +2260,9 @@ extern "C" int cake_hip_op_kv_store(int S, int pos0, int decode, int nh,
   const size_t ncache = (size_t)nkv * max_seq * hd;
   const size_t ntab = (size_t)max_seq * (hd / 2);
   u16 *dqkv, *dkc, *dvc, *dvtc, *dqn = nullptr, *dkn = nullptr;
-  void *dcos, *dsin, *dpos;
+  void *dcos, *dsin, *dpos, *dbias = nullptr;
   if ((r = ob_up16(b, qkv, (size_t)S * Nq, &dqkv))) return r;
+  if (bias && (r = ob_upf32(b, bias, (size_t)Nq * 4, &dbias))) return r;
   if ((r = ob_up16(b, kc, ncache, &dkc))) return r;
   if ((r = ob_up16(b, vc, ncache, &dvc))) return r;
   if ((r = ob_up16(b, vtc, ncache, &dvtc))) return r;
@@ -2195,11 +2276,13 @@ extern "C" int cake_hip_op_kv_store(int S, int pos0, int decode, int nh,
   if (decode)
     launch_rope_store_decode(dqkv, dkc, dvc, dvtc, (const float*)dcos,
                              (const float*)dsin, (const int*)dpos, nh, nkv,
-                             hd, hd, max_seq, dqn, dkn, eps, b.s);
+                             hd, hd, max_seq, dqn, dkn, eps, b.s,
+                             (const float*)dbias);
   else
     launch_rope_store_prefill(dqkv, dkc, dvc, dvtc, (const float*)dcos,
                               (const float*)dsin, pos0, S, nh, nkv, hd, hd,
-                              max_seq, Nq, dqn, dkn, eps, b.s);
+                              max_seq, Nq, dqn, dkn, eps, b.s,
+                              (const float*)dbias);
   HIP_TRY(hipGetLastError());
   std::vector<float> rows((size_t)S * Nq);
   if ((r = ob_down16(b, dqkv, rows.size(), rows.data()))) return r;
@@ -2209,6 +2292,30 @@ extern "C" int cake_hip_op_kv_store(int S, int pos0, int decode, int nh,
   if ((r = ob_down16(b, dkc, ncache, kc))) return r;
   if ((r = ob_down16(b, dvc, ncache, vc))) return r;
   return ob_down16(b, dvtc, ncache, vtc);
+}
+extern "C" int cake_hip_op_kv_store(int S, int pos0, int decode, int nh,
+                                    int nkv, int hd, int max_seq,
+                                    const float* qkv, const float* cosv,
+                                    const float* sinv, const float* q_norm,
+                                    const float* k_norm, float eps, float* kc,
+                                    float* vc, float* vtc, float* q_out,
+                                    int device) {
+  return op_kv_store_impl("op_kv_store", S, pos0, decode, nh, nkv, hd,
+                          max_seq, qkv, cosv, sinv, q_norm, k_norm, eps,
+                          nullptr, kc, vc, vtc, q_out, device);
+}
+extern "C" int cake_hip_op_kv_store_bias(int S, int pos0, int decode, int nh,
+                                         int nkv, int hd, int max_seq,
+                                         const float* qkv, const float* cosv,
+                                         const float* sinv,
+                                         const float* q_norm,
+                                         const float* k_norm, float eps,
+                                         const float* bias, float* kc,
+                                         float* vc, float* vtc, float* q_out,
+                                         int device) {
+  return op_kv_store_impl("op_kv_store_bias", S, pos0, decode, nh, nkv, hd,
+                          max_seq, qkv, cosv, sinv, q_norm, k_norm, eps, bias,
+                          kc, vc, vtc, q_out, device);
 }
 
 extern "C" int cake_hip_op_attn_prefill(int S, int pos0, int nh, int nkv,
@@ -2592,14 +2699,13 @@ extern "C" int cake_hip_op_gemv_gateup(int fp8, int I, int K, int rows,
   return ob_down16(b, dout, (size_t)I + OPG, out);
 }
 
-extern "C" int cake_hip_op_gemv_qkv_rope(int nh, int nkv, int hd, int max_seq,
-                                         int pos, int K, const float* x,
-                                         const float* nw, float eps,
-                                         const float* w, const float* cosv,
-                                         const float* sinv, float* kc,
-                                         float* vc, float* vtc, float* out,
-                                         int device) {
-  const char* who = "op_gemv_qkv_rope";
+// shared body of cake_hip_op_gemv_qkv_rope[_bias]; bias may be null
+static int op_gemv_qkv_rope_impl(const char* who, int nh, int nkv, int hd,
+                                 int max_seq, int pos, int K, const float* x,
+                                 const float* nw, float eps, const float* w,
+                                 const float* cosv, const float* sinv,
+                                 const float* bias, float* kc, float* vc,
+                                 float* vtc, float* out, int device) {
   int r = attn_geom_err(who, nh, nkv, hd, max_seq);
   if (r) return r;
   if (pos < 0 || pos >= max_seq)
@@ -2617,8 +2723,9 @@ extern "C" int cake_hip_op_gemv_qkv_rope(int nh, int nkv, int hd, int max_seq,
   const size_t ncache = (size_t)nkv * max_seq * hd;
   const size_t ntab = (size_t)max_seq * (hd / 2);
   u16 *dx, *dnw, *dw, *dkc, *dvc, *dvtc, *dout;
-  void *dcos, *dsin, *dpos;
+  void *dcos, *dsin, *dpos, *dbias = nullptr;
   if ((r = ob_up16(b, x, K, &dx))) return r;
+  if (bias && (r = ob_upf32(b, bias, (size_t)Nq * 4, &dbias))) return r;
   if ((r = ob_up16(b, nw, K, &dnw))) return r;
   if ((r = ob_up16(b, w, (size_t)Nq * K, &dw))) return r;
   if ((r = ob_up16(b, kc, ncache, &dkc))) return r;
@@ -2631,12 +2738,33 @@ extern "C" int cake_hip_op_gemv_qkv_rope(int nh, int nkv, int hd, int max_seq,
   if ((r = ob_sent16(b, (size_t)Nq + OPG, &dout))) return r;
   launch_gemv_qkv_rope(dw, dx, dout, dnw, eps, dkc, dvc, dvtc,
                        (const float*)dcos, (const float*)dsin,
-                       (const int*)dpos, nh, nkv, hd, max_seq, K, b.s);
+                       (const int*)dpos, nh, nkv, hd, max_seq, K, b.s,
+                       (const float*)dbias);
   HIP_TRY(hipGetLastError());
   if ((r = ob_down16(b, dout, (size_t)Nq + OPG, out))) return r;
   if ((r = ob_down16(b, dkc, ncache, kc))) return r;
   if ((r = ob_down16(b, dvc, ncache, vc))) return r;
   return ob_down16(b, dvtc, ncache, vtc);
+}
+extern "C" int cake_hip_op_gemv_qkv_rope(int nh, int nkv, int hd, int max_seq,
+                                         int pos, int K, const float* x,
+                                         const float* nw, float eps,
+                                         const float* w, const float* cosv,
+                                         const float* sinv, float* kc,
+                                         float* vc, float* vtc, float* out,
+                                         int device) {
+  return op_gemv_qkv_rope_impl("op_gemv_qkv_rope", nh, nkv, hd, max_seq, pos,
+                               K, x, nw, eps, w, cosv, sinv, nullptr, kc, vc,
+                               vtc, out, device);
+}
+extern "C" int cake_hip_op_gemv_qkv_rope_bias(
+    int nh, int nkv, int hd, int max_seq, int pos, int K, const float* x,
+    const float* nw, float eps, const float* w, const float* cosv,
+    const float* sinv, const float* bias, float* kc, float* vc, float* vtc,
+    float* out, int device) {
+  return op_gemv_qkv_rope_impl("op_gemv_qkv_rope_bias", nh, nkv, hd, max_seq,
+                               pos, K, x, nw, eps, w, cosv, sinv, bias, kc, vc,
+                               vtc, out, device);
 }
 
 extern "C" int cake_hip_op_gemm(int variant, int M, int N, int K, int epi,

@@ -41,12 +41,22 @@ void launch_gemv_gateup(const u16* W, const u16* x, u16* out, const u16* nw,
 void launch_gemv_res_splitk(const u16* W, const u16* x, u16* out,
                             const u16* res, float* ws, u32* cnt, int N,
                             int K, hipStream_t s);
-// fused rms_norm -> qkv GEMV -> rope -> KV-cache store (llama family)
+// fused rms_norm -> qkv GEMV -> rope -> KV-cache store (llama family).
+// bias: the fused q|k|v projection bias row (Nq f32, qwen2) added to the f32
+// sums; non-null runs k_gemv_qkv_rope_bias (kernels_qkv_bias.hip), null the
+// unbiased kernel.
 void launch_gemv_qkv_rope(const u16* W, const u16* x, u16* out, const u16* nw,
                           float eps, u16* kc, u16* vc, u16* vtc,
                           const float* cost, const float* sint,
                           const int* pos, int nh, int nkv, int hd,
-                          int max_seq, int K, hipStream_t s);
+                          int max_seq, int K, hipStream_t s,
+                          const float* bias = nullptr);
+void launch_gemv_qkv_rope_bias(const u16* W, const u16* x, u16* out,
+                               const u16* nw, float eps, u16* kc, u16* vc,
+                               u16* vtc, const float* cost, const float* sint,
+                               const int* pos, const float* bias, int nh,
+                               int nkv, int hd, int max_seq, int K,
+                               hipStream_t s);
 // fp8 decode norm chain (replaces the split-norm rmsnorm LAUNCHES): the
 // x-producing GEMV's epilogue publishes per-block sumsq partials of its
 // QUANTIZED outputs; its last-arriving block reduces them in fixed order
@@ -95,16 +105,20 @@ void launch_embed_token(const u16* embed, const u32* tok, u16* x, int H,
                         float eps = 1e-5f);
 void launch_embed_rows(const u16* embed, const u32* ids, u16* x, int S, int H,
                        hipStream_t s);
+// bias: the fused q|k|v projection bias row ((nh + 2*nkv)*hd f32, qwen2), added
+// to the raw row in f32 before the rotation / the V store; null = none
 void launch_rope_store_decode(u16* qkv, u16* kc, u16* vc, u16* vtc,
                               const float* cost, const float* sint,
                               const int* pos, int nh, int nkv, int hd, int rd,
                               int max_seq, const u16* qn, const u16* kn,
-                              float eps, hipStream_t s);
+                              float eps, hipStream_t s,
+                              const float* bias = nullptr);
 void launch_rope_store_prefill(u16* qkv, u16* kc, u16* vc, u16* vtc,
                                const float* cost, const float* sint, int pos0,
                                int S, int nh, int nkv, int hd, int rd,
                                int max_seq, int qkv_stride, const u16* qn,
-                               const u16* kn, float eps, hipStream_t s);
+                               const u16* kn, float eps, hipStream_t s,
+                               const float* bias = nullptr);
 void launch_attn_decode(const u16* q, const u16* kc, const u16* vc,
                         const int* pos, float* ws, u32* cnt, u16* out, int nh,
                         int nkv, int hd, int max_seq, int nchunk, int window,

@@ -12,6 +12,10 @@
 // Optional fused per-head QK-norm (attention.rs:202-215): applied to the
 // head row before the rotation, re-quantized to bf16 so it matches the
 // separate rmsnorm-kernel path bit-exactly.  One wave per head.
+// Optional q|k|v projection bias (qwen2; `bias` = the fused (nh+2*nkv)*hd f32
+// row, or null): every raw value gets float(raw) + bias[row] in f32, ahead of
+// the rotation for q and k and ahead of the store for v, with no rounding in
+// between.  A null bias leaves every output bit as it was.
 __device__ inline float head_norm_scale(const u16* row, int hd, float eps) {
   float ss = 0.f;
   for (int i = threadIdx.x; i < hd; i += 64) {
@@ -36,18 +40,25 @@ __global__ void k_rope_store_decode(u16* __restrict__ qkv,
                                     const int* __restrict__ pos, int nh,
                                     int nkv, int hd, int rd, int max_seq,
                                     const u16* __restrict__ qn,
-                                    const u16* __restrict__ kn, float eps) {
+                                    const u16* __restrict__ kn, float eps,
+                                    const float* __restrict__ bias) {
   const int b = blockIdx.x;
   const int p = *pos;
   const int half = rd / 2;
   const float* c = cost + (size_t)p * half;
   const float* s = sint + (size_t)p * half;
+  // this head's slice of the fused q|k|v projection bias (qwen2), or null
+  const float* br = bias ? bias + (size_t)b * hd : nullptr;
   if (b < nh) {                       // [qk-norm +] rope q head in place
     u16* q = qkv + (size_t)b * hd;
     const bool on = qn != nullptr;
     const float sc = on ? head_norm_scale(q, hd, eps) : 1.f;
     for (int i = threadIdx.x; i < half; i += blockDim.x) {
       float x1 = nrm(q, qn, i, sc, on), x2 = nrm(q, qn, i + half, sc, on);
+      if (br) {
+        x1 += br[i];
+        x2 += br[i + half];
+      }
       q[i] = f2b(x1 * c[i] - x2 * s[i]);
       q[i + half] = f2b(x2 * c[i] + x1 * s[i]);
     }
@@ -59,18 +70,24 @@ __global__ void k_rope_store_decode(u16* __restrict__ qkv,
     const float sc = on ? head_norm_scale(k, hd, eps) : 1.f;
     for (int i = threadIdx.x; i < half; i += blockDim.x) {
       float x1 = nrm(k, kn, i, sc, on), x2 = nrm(k, kn, i + half, sc, on);
+      if (br) {
+        x1 += br[i];
+        x2 += br[i + half];
+      }
       dst[i] = f2b(x1 * c[i] - x2 * s[i]);
       dst[i + half] = f2b(x2 * c[i] + x1 * s[i]);
     }
-    for (int i = rd + threadIdx.x; i < hd; i += blockDim.x) dst[i] = k[i];
+    for (int i = rd + threadIdx.x; i < hd; i += blockDim.x)
+      dst[i] = br ? f2b(b2f(k[i]) + br[i]) : k[i];
   } else {                            // v head -> cache slot p (+ V^T)
     const int h = b - nh - nkv;
     const u16* v = qkv + (size_t)(nh + nkv + h) * hd;
     u16* dst = vc + ((size_t)h * max_seq + p) * hd;
     u16* dstt = vtc + (size_t)h * hd * max_seq + p;
     for (int i = threadIdx.x; i < hd; i += blockDim.x) {
-      dst[i] = v[i];
-      dstt[(size_t)i * max_seq] = v[i];
+      const u16 e = br ? f2b(b2f(v[i]) + br[i]) : v[i];
+      dst[i] = e;
+      dstt[(size_t)i * max_seq] = e;
     }
   }
 }
@@ -85,7 +102,8 @@ __global__ void k_rope_store_prefill(u16* __restrict__ qkv,
                                      int nh, int nkv, int hd, int rd,
                                      int max_seq, int qkv_stride,
                                      const u16* __restrict__ qn,
-                                     const u16* __restrict__ kn, float eps) {
+                                     const u16* __restrict__ kn, float eps,
+                                     const float* __restrict__ bias) {
   const int b = blockIdx.x;
   const int sidx = blockIdx.y;
   const int p = pos0 + sidx;
@@ -93,12 +111,17 @@ __global__ void k_rope_store_prefill(u16* __restrict__ qkv,
   const float* c = cost + (size_t)p * half;
   const float* s = sint + (size_t)p * half;
   u16* row = qkv + (size_t)sidx * qkv_stride;
+  const float* br = bias ? bias + (size_t)b * hd : nullptr;
   if (b < nh) {
     u16* q = row + (size_t)b * hd;
     const bool on = qn != nullptr;
     const float sc = on ? head_norm_scale(q, hd, eps) : 1.f;
     for (int i = threadIdx.x; i < half; i += blockDim.x) {
       float x1 = nrm(q, qn, i, sc, on), x2 = nrm(q, qn, i + half, sc, on);
+      if (br) {
+        x1 += br[i];
+        x2 += br[i + half];
+      }
       q[i] = f2b(x1 * c[i] - x2 * s[i]);
       q[i + half] = f2b(x2 * c[i] + x1 * s[i]);
     }
@@ -110,18 +133,24 @@ __global__ void k_rope_store_prefill(u16* __restrict__ qkv,
     const float sc = on ? head_norm_scale(k, hd, eps) : 1.f;
     for (int i = threadIdx.x; i < half; i += blockDim.x) {
       float x1 = nrm(k, kn, i, sc, on), x2 = nrm(k, kn, i + half, sc, on);
+      if (br) {
+        x1 += br[i];
+        x2 += br[i + half];
+      }
       dst[i] = f2b(x1 * c[i] - x2 * s[i]);
       dst[i + half] = f2b(x2 * c[i] + x1 * s[i]);
     }
-    for (int i = rd + threadIdx.x; i < hd; i += blockDim.x) dst[i] = k[i];
+    for (int i = rd + threadIdx.x; i < hd; i += blockDim.x)
+      dst[i] = br ? f2b(b2f(k[i]) + br[i]) : k[i];
   } else {
     const int h = b - nh - nkv;
     const u16* v = row + (size_t)(nh + nkv + h) * hd;
     u16* dst = vc + ((size_t)h * max_seq + p) * hd;
     u16* dstt = vtc + (size_t)h * hd * max_seq + p;
     for (int i = threadIdx.x; i < hd; i += blockDim.x) {
-      dst[i] = v[i];
-      dstt[(size_t)i * max_seq] = v[i];
+      const u16 e = br ? f2b(b2f(v[i]) + br[i]) : v[i];
+      dst[i] = e;
+      dstt[(size_t)i * max_seq] = e;
     }
   }
 }
@@ -1668,19 +1697,20 @@ void launch_rope_store_decode(u16* qkv, u16* kc, u16* vc, u16* vtc,
                               const float* cost, const float* sint,
                               const int* pos, int nh, int nkv, int hd, int rd,
                               int max_seq, const u16* qn, const u16* kn,
-                              float eps, hipStream_t s) {
+                              float eps, hipStream_t s, const float* bias) {
   hipLaunchKernelGGL(k_rope_store_decode, dim3(nh + 2 * nkv), dim3(64), 0, s,
                      qkv, kc, vc, vtc, cost, sint, pos, nh, nkv, hd, rd,
-                     max_seq, qn, kn, eps);
+                     max_seq, qn, kn, eps, bias);
 }
 void launch_rope_store_prefill(u16* qkv, u16* kc, u16* vc, u16* vtc,
                                const float* cost, const float* sint, int pos0,
                                int S, int nh, int nkv, int hd, int rd,
                                int max_seq, int qkv_stride, const u16* qn,
-                               const u16* kn, float eps, hipStream_t s) {
+                               const u16* kn, float eps, hipStream_t s,
+                               const float* bias) {
   hipLaunchKernelGGL(k_rope_store_prefill, dim3(nh + 2 * nkv, S), dim3(64), 0,
                      s, qkv, kc, vc, vtc, cost, sint, pos0, nh, nkv, hd, rd,
-                     max_seq, qkv_stride, qn, kn, eps);
+                     max_seq, qkv_stride, qn, kn, eps, bias);
 }
 void launch_attn_decode(const u16* q, const u16* kc, const u16* vc,
                         const int* pos, float* ws, u32* cnt, u16* out, int nh,

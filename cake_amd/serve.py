@@ -294,9 +294,8 @@ def main():
     args = ap.parse_args()
 
     import cake_amd
-    from cake_amd.configs import MODELS, QUANT_MODELS
-    cfg = MODELS[args.model] if args.model in MODELS else \
-        QUANT_MODELS[args.model]
+    from cake_amd.configs import find_model
+    cfg = find_model(args.model)
     eng = cake_amd.Engine(json.dumps(cfg), max_seq=args.max_seq,
                           max_batch_tokens=2048)
     if args.safetensors:

@@ -78,11 +78,18 @@ void cake_hip_engine_free(cake_engine *e);
  * upload straight to HBM as bf16.  F32, F16 and BF16 source dtypes accepted.
  * quantization_config.quant_method selects the weight format: "fp8"
  * (weight + weight_scale_inv) or "gptq" (4-bit qweight / qzeros / scales,
- * kept packed in HBM; bits 4, desc_act false, group_size % 32 == 0). */
+ * kept packed in HBM; bits 4, desc_act false, group_size % 32 == 0).
+ * model_type "qwen2" (Qwen2 / Qwen2.5) additionally REQUIRES
+ * model.layers.N.self_attn.{q,k,v}_proj.bias (F32, F16 or BF16, one
+ * dimension) in every weight format; they are kept as one fused f32 row per
+ * layer, and a missing or mis-shaped one is an error that names the tensor.
+ * Other model types ignore bias tensors; a config with attention_bias or
+ * mlp_bias true on another model type is refused at create (error 5). */
 int cake_hip_load_safetensors(cake_engine *e, const char *path);
 
 /* Seeded random init on device (synthetic-weights benches; no network for
- * checkpoints).  RMS weights = 1, linear weights ~ scale * uniform(-1,1). */
+ * checkpoints).  RMS weights = 1, linear weights ~ scale * uniform(-1,1);
+ * qwen2's q/k bias rows ~ uniform(-3,3), its v rows ~ uniform(-.25,.25). */
 int cake_hip_init_random(cake_engine *e, uint64_t seed, float scale);
 
 /* ---- generation ----------------------------------------------------------
@@ -170,6 +177,17 @@ int cake_hip_op_kv_store(int S, int pos0, int decode, int nh, int nkv, int hd,
                          const float *sinv, const float *q_norm,
                          const float *k_norm, float eps, float *kc, float *vc,
                          float *vtc, float *q_out, int device);
+/* kv_store with the q|k|v projection bias of qwen2: bias ((nh+2*nkv)*hd f32,
+ * may be NULL) is added to every raw row in f32 ahead of the rotation (q, k)
+ * and of the store (v).  NULL is op_kv_store bit for bit.  A bias together
+ * with q_norm/k_norm is refused (error 5). */
+int cake_hip_op_kv_store_bias(int S, int pos0, int decode, int nh, int nkv,
+                              int hd, int max_seq, const float *qkv,
+                              const float *cosv, const float *sinv,
+                              const float *q_norm, const float *k_norm,
+                              float eps, const float *bias, float *kc,
+                              float *vc, float *vtc, float *q_out,
+                              int device);
 /* Causal [sliding-window] GQA attention of S post-rope q rows (S, nh*hd) at
  * positions pos0.. over the cache images; out (S, nh*hd).  Variant: hd 128
  * takes pfv 1 (nw 8, no split/deep) or pfv 2 with nw 4|8 and at most one of
@@ -252,6 +270,14 @@ int cake_hip_op_gemv_qkv_rope(int nh, int nkv, int hd, int max_seq, int pos,
                               float eps, const float *w, const float *cosv,
                               const float *sinv, float *kc, float *vc,
                               float *vtc, float *out, int device);
+/* The same with the bias row of op_kv_store_bias: non-NULL runs the biased
+ * kernel (bias joins the f32 sums), NULL the unbiased one. */
+int cake_hip_op_gemv_qkv_rope_bias(int nh, int nkv, int hd, int max_seq,
+                                   int pos, int K, const float *x,
+                                   const float *nw, float eps, const float *w,
+                                   const float *cosv, const float *sinv,
+                                   const float *bias, float *kc, float *vc,
+                                   float *vtc, float *out, int device);
 /* C[M,N] = A[M,K] @ W[N,K]^T (+ res) by an explicit variant: 0 128^2 tile,
  * 1 256^2, 2 128x256, 3 256^2 fine-phase, 4 hipBLASLt.  Variants 1..3 need
  * K % 64 == 0 (any number of 64-wide tiles >= 1); 0 and 4 take K % 8 == 0.

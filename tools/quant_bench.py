@@ -27,7 +27,8 @@ SEED = 299792458
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("model", help="a name from MODELS or QUANT_MODELS")
+    ap.add_argument("model", help="a name from MODELS, QUANT_MODELS or "
+                    "QWEN2_MODELS")
     ap.add_argument("--steps", type=int, default=256)
     ap.add_argument("--prompt-len", type=int, default=128)
     ap.add_argument("--max-seq", type=int, default=4096)
@@ -37,9 +38,8 @@ def main():
     args = ap.parse_args()
 
     import cake_amd
-    from cake_amd.configs import MODELS, QUANT_MODELS, weight_bytes
-    cfg = MODELS[args.model] if args.model in MODELS else \
-        QUANT_MODELS[args.model]
+    from cake_amd.configs import find_model, weight_bytes
+    cfg = find_model(args.model)
     flags = cake_amd.HAS_EMBED | cake_amd.HAS_HEAD | cake_amd.USE_GRAPH
     eng = cake_amd.Engine(json.dumps(cfg), flags=flags, max_seq=args.max_seq,
                           max_batch_tokens=2048)
