@@ -65,6 +65,8 @@ def _load_lib():
                                          fp, f, fp, fp, fp, fp, c]
     lib.cake_hip_op_kv_store_bias.argtypes = [c] * 7 + [fp] * 5 + [f] + \
         [fp] * 5 + [c]
+    lib.cake_hip_op_kv_store_pr.argtypes = [c] * 8 + [fp] * 5 + [f] + \
+        [fp] * 4 + [c]
     lib.cake_hip_op_attn_prefill.argtypes = [c] * 11 + [fp] * 5 + [c]
     lib.cake_hip_op_attn_decode.argtypes = [c] * 8 + [fp] * 4 + [c]
     lib.cake_hip_attn_dispatch.argtypes = [c, c, c, c, ctypes.POINTER(c)]
@@ -80,6 +82,8 @@ def _load_lib():
         [fp] * 7 + [c]
     lib.cake_hip_op_gemv_qkv_rope_bias.argtypes = [c] * 6 + [fp, fp, f] + \
         [fp] * 8 + [c]
+    lib.cake_hip_op_gemv_qkv_rope_pr.argtypes = [c] * 7 + [fp, fp, f] + \
+        [fp] * 7 + [c]
     lib.cake_hip_op_gemm.argtypes = [c] * 6 + [fp, fp, fp, fp,
                                                ctypes.POINTER(c), c]
     lib.cake_hip_op_dequant_fp8.argtypes = [c, c, u8p, fp, fp, c]
@@ -89,6 +93,7 @@ def _load_lib():
     lib.cake_hip_linear_dispatch.argtypes = [c, c, c, c, c,
                                              ctypes.POINTER(c)]
     lib.cake_hip_decode_dispatch.argtypes = [cp, ctypes.POINTER(c)]
+    lib.cake_hip_rope_tables.argtypes = [cp, c, fp, fp, ctypes.POINTER(c)]
     i32p = ctypes.POINTER(ctypes.c_int32)
     lib.cake_hip_op_gemv_w4.argtypes = [c] * 7 + [fp, i32p, i32p, fp, fp, fp,
                                                   c]
@@ -226,10 +231,21 @@ def op_kv_store_bias(qkv, bias, cos, sin, kc, vc, vtc, pos0, nh, nkv,
                         q_norm, k_norm, eps, decode, device)
 
 
+def op_kv_store_pr(qkv, cos, sin, kc, vc, vtc, pos0, nh, nkv, rd,
+                   q_norm=None, k_norm=None, eps=1e-6, decode=False,
+                   device=0):
+    """op_kv_store through cake_hip_op_kv_store_pr: partial rotary, only the
+    first rd dims of each q and k head rotate; cos / sin are (max_seq,
+    rd/2)."""
+    return _op_kv_store(False, None, qkv, cos, sin, kc, vc, vtc, pos0, nh,
+                        nkv, q_norm, k_norm, eps, decode, device, rd=rd)
+
+
 def _op_kv_store(bias_entry, bias, qkv, cos, sin, kc, vc, vtc, pos0, nh, nkv,
-                 q_norm, k_norm, eps, decode, device):
+                 q_norm, k_norm, eps, decode, device, rd=None):
     kc = np.array(kc, dtype=np.float32, order="C")
     nkv_, max_seq, hd = kc.shape if kc.ndim == 3 else (0, 0, 0)
+    half = (hd if rd is None else rd) // 2
     qkv = np.ascontiguousarray(qkv, dtype=np.float32)
     S = qkv.shape[0]
     _, qp = _f32_shaped(qkv, (S, (nh + 2 * nkv) * hd), "qkv")
@@ -238,8 +254,8 @@ def _op_kv_store(bias_entry, bias, qkv, cos, sin, kc, vc, vtc, pos0, nh, nkv,
                          (nkv, max_seq, hd), "vc")
     vtc, vtp = _f32_shaped(np.array(vtc, dtype=np.float32, order="C"),
                            (nkv, hd, max_seq), "vtc")
-    _c, cp = _f32_shaped(cos, (max_seq, hd // 2), "cos")
-    _s, sp = _f32_shaped(sin, (max_seq, hd // 2), "sin")
+    _c, cp = _f32_shaped(cos, (max_seq, half), "cos")
+    _s, sp = _f32_shaped(sin, (max_seq, half), "sin")
     qn = kn = qnp = knp = None
     if q_norm is not None:
         qn, qnp = _f32_shaped(q_norm, (hd,), "q_norm")
@@ -250,7 +266,9 @@ def _op_kv_store(bias_entry, bias, qkv, cos, sin, kc, vc, vtc, pos0, nh, nkv,
             qnp, knp, ctypes.c_float(eps))
     tail = (kp, vp, vtp,
             q_out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), device)
-    if bias_entry:
+    if rd is not None:
+        _check(_lib.cake_hip_op_kv_store_pr(*head[:6], rd, *head[6:], *tail))
+    elif bias_entry:
         _b, bp = _opt_f32(bias, ((nh + 2 * nkv) * hd,), "bias")
         _check(_lib.cake_hip_op_kv_store_bias(*head, bp, *tail))
     else:
@@ -472,18 +490,28 @@ def op_gemv_qkv_rope_bias(x, nw, w, bias, cos, sin, kc, vc, vtc, pos, nh, nkv,
                              nh, nkv, eps, device)
 
 
+def op_gemv_qkv_rope_pr(x, nw, w, cos, sin, kc, vc, vtc, pos, nh, nkv, rd,
+                        eps=1e-5, device=0):
+    """op_gemv_qkv_rope through cake_hip_op_gemv_qkv_rope_pr: partial rotary
+    over the first rd dims of each head, cos / sin (max_seq, rd/2); rd < hd
+    runs k_gemv_qkv_rope_pr, rd == hd the full-rotation kernel."""
+    return _op_gemv_qkv_rope(False, None, x, nw, w, cos, sin, kc, vc, vtc,
+                             pos, nh, nkv, eps, device, rd=rd)
+
+
 def _op_gemv_qkv_rope(bias_entry, bias, x, nw, w, cos, sin, kc, vc, vtc, pos,
-                      nh, nkv, eps, device):
+                      nh, nkv, eps, device, rd=None):
     kc = np.array(kc, dtype=np.float32, order="C")
     nkv_, max_seq, hd = kc.shape
+    half = (hd if rd is None else rd) // 2
     x = np.ascontiguousarray(x, dtype=np.float32)
     K = x.shape[0]
     Nq = (nh + 2 * nkv) * hd
     _, xp = _f32_shaped(x, (K,), "x")
     _n, nwp = _f32_shaped(nw, (K,), "nw")
     _w, wp = _f32_shaped(w, (Nq, K), "w")
-    _c, cp = _f32_shaped(cos, (max_seq, hd // 2), "cos")
-    _s, sp = _f32_shaped(sin, (max_seq, hd // 2), "sin")
+    _c, cp = _f32_shaped(cos, (max_seq, half), "cos")
+    _s, sp = _f32_shaped(sin, (max_seq, half), "sin")
     kc, kp = _f32_shaped(kc, (nkv, max_seq, hd), "kc")
     vc, vp = _f32_shaped(np.array(vc, dtype=np.float32, order="C"),
                          (nkv, max_seq, hd), "vc")
@@ -493,7 +521,10 @@ def _op_gemv_qkv_rope(bias_entry, bias, x, nw, w, cos, sin, kc, vc, vtc, pos,
     head = (nh, nkv, hd, max_seq, pos, K, xp, nwp, eps, wp, cp, sp)
     tail = (kp, vp, vtp, out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
             device)
-    if bias_entry:
+    if rd is not None:
+        _check(_lib.cake_hip_op_gemv_qkv_rope_pr(*head[:3], rd, *head[3:],
+                                                 *tail))
+    elif bias_entry:
         _b, bp = _opt_f32(bias, (Nq,), "bias")
         _check(_lib.cake_hip_op_gemv_qkv_rope_bias(*head, bp, *tail))
     else:
@@ -722,6 +753,26 @@ def decode_dispatch(config):
     _check(_lib.cake_hip_decode_dispatch(config.encode(), o))
     return {k: (LINEAR_FAMILIES[o[3 * i]], o[3 * i + 1], o[3 * i + 2])
             for i, k in enumerate(("qkv", "o", "gateup", "down", "head"))}
+
+
+def rope_tables(config, max_seq):
+    """The rope tables engine create builds for this config and max_seq (host
+    only, same function): (cos, sin), each (max_seq, rd/2) f32, rd the rotated
+    dims of a head (partial_rotary_factor); LongRoPE's list choice and
+    attention factor included."""
+    if isinstance(config, dict):
+        config = json.dumps(config)
+    rd = ctypes.c_int(0)
+    _check(_lib.cake_hip_rope_tables(config.encode(), max_seq, None, None,
+                                     ctypes.byref(rd)))
+    cos = np.empty((max_seq, rd.value // 2), dtype=np.float32)
+    sin = np.empty_like(cos)
+    fpt = ctypes.POINTER(ctypes.c_float)
+    _check(_lib.cake_hip_rope_tables(config.encode(), max_seq,
+                                     cos.ctypes.data_as(fpt),
+                                     sin.ctypes.data_as(fpt),
+                                     ctypes.byref(rd)))
+    return cos, sin
 
 
 def comm_id() -> bytes:

@@ -77,6 +77,36 @@ QWEN2_5_7B_GPTQ = dict(QWEN2_5_7B,
     quantization_config=dict(quant_method="gptq", bits=4, group_size=128,
                              desc_act=False, sym=True))
 
+# Phi-4 family (phi4/, HF model_type "phi3"): llama-shaped, but the checkpoint
+# ships self_attn.qkv_proj and mlp.gate_up_proj fused (phi4/config.rs:88-89).
+# Phi-4-mini also rotates only the first 96 of 128 head dims and scales its
+# frequencies by LongRoPE.
+PHI_4 = dict(
+    model_type="phi3", hidden_size=5120, intermediate_size=17920,
+    vocab_size=100352, num_hidden_layers=40, num_attention_heads=40,
+    num_key_value_heads=10, rms_norm_eps=1e-5, rope_theta=250000.0,
+    max_position_embeddings=16384, tie_word_embeddings=False)
+
+# The published 48-entry short_factor / long_factor lists are not reproduced
+# here: these are monotone PLACEHOLDERS of the right length (short 1.0 .. 1.5,
+# long 1.0 .. 30).  They set table values only and do not affect speed; a real
+# run takes the lists from the checkpoint's config.json.
+PHI_4_MINI = dict(
+    model_type="phi3", hidden_size=3072, intermediate_size=8192,
+    vocab_size=200064, num_hidden_layers=32, num_attention_heads=24,
+    num_key_value_heads=8, head_dim=128, rms_norm_eps=1e-5,
+    rope_theta=10000.0, partial_rotary_factor=0.75,
+    max_position_embeddings=131072, original_max_position_embeddings=4096,
+    tie_word_embeddings=True,
+    rope_scaling=dict(
+        type="longrope",
+        short_factor=[1.0 + 0.5 * i / 47 for i in range(48)],
+        long_factor=[1.0 + 29.0 * i / 47 for i in range(48)]))
+
+PHI_4_GPTQ = dict(PHI_4,
+    quantization_config=dict(quant_method="gptq", bits=4, group_size=128,
+                             desc_act=False, sym=True))
+
 MODELS = {
     "llama3-8b": LLAMA3_8B,
     "llama3-70b": LLAMA3_70B,
@@ -101,9 +131,19 @@ QWEN2_MODELS = {
 }
 
 
+# the phi3 family (fused checkpoint tensors; partial rotary and LongRoPE in
+# phi-4-mini)
+PHI_MODELS = {
+    "phi-4": PHI_4,
+    "phi-4-mini": PHI_4_MINI,
+    "phi-4-gptq": PHI_4_GPTQ,
+}
+
+
 def find_model(name: str) -> dict:
-    """The config called `name` in MODELS, QUANT_MODELS or QWEN2_MODELS."""
-    for table in (MODELS, QUANT_MODELS, QWEN2_MODELS):
+    """The config called `name` in MODELS, QUANT_MODELS, QWEN2_MODELS or
+    PHI_MODELS."""
+    for table in (MODELS, QUANT_MODELS, QWEN2_MODELS, PHI_MODELS):
         if name in table:
             return table[name]
     raise KeyError(name)

@@ -9,7 +9,11 @@
 //   - the generation loop (text_model.rs:266-368,397-495): greedy ArgMax,
 //     KV-cached decode with context size 1
 //   - the Cache (cache.rs): preallocated device KV cache (no cat-per-token),
-//     host-precomputed f32 RoPE tables incl. llama3 scaling (cache.rs:43-99)
+//     host-precomputed f32 RoPE tables incl. llama3 scaling (cache.rs:43-99),
+//     partial rotary (phi4/attention.rs:59-66) and LongRoPE as HF
+//     transformers computes it, with ONE factor list per engine: long_factor
+//     if max_seq exceeds original_max_position_embeddings, else short_factor
+//     (HF switches per call and drops its cache; build_rope_tables)
 //   - the cluster transport (client.rs/worker.rs/proto/message.rs): the
 //     per-token activation hop is RCCL ncclSend/ncclRecv over xGMI between
 //     adjacent ranks holding contiguous layer ranges
@@ -95,8 +99,21 @@ struct ModelConfig {
   bool rope_llama3 = false;
   float rs_factor = 1, rs_low = 1, rs_high = 4;
   float rs_orig = 0;
+  // phi3 (Phi-3 / Phi-4): the checkpoint ships self_attn.qkv_proj and
+  // mlp.gate_up_proj already fused (phi4/config.rs:88-89)
+  bool fused_ckpt = false;
+  // partial rotary (phi4/attention.rs:59-66): only the first rd() dims of a
+  // head rotate; any model type
+  float rotary_factor = 1.f;
+  // LongRoPE ("longrope" / "su", HF _compute_longrope_parameters): one divisor
+  // per frequency, short or long list by max_seq, and an attention factor on
+  // cos and sin.  lr_factor / lr_attn 0 = absent.
+  bool rope_long = false;
+  std::vector<float> lr_short, lr_long;
+  float lr_orig = 0, lr_factor = 0, lr_attn = 0;
 
   int hd() const { return head_dim ? head_dim : hidden / nh; }
+  int rd() const { return (int)((float)hd() * rotary_factor); }
   int sq() const { return nh * hd(); }
   int skv() const { return nkv * hd(); }
   int nqkv() const { return sq() + 2 * skv(); }
@@ -131,6 +148,10 @@ static int parse_config(const char* json, ModelConfig* c) {
     c->qkv_bias = p->str == "qwen2";
     // qwen2's own default (qwen2/config.rs:7-9)
     if (c->qkv_bias && !v->get("rope_theta")) c->rope_theta = 1e6f;
+    // phi3: fused checkpoint tensors; defaults of phi4/config.rs:7-9, 64
+    // (num_key_value_heads already defaults to the head count above)
+    c->fused_ckpt = p->str == "phi3";
+    if (c->fused_ckpt && !v->get("rope_theta")) c->rope_theta = 1e6f;
   }
   // A bias this engine would silently drop is refused: only qwen2's q/k/v
   // bias is implemented (no o-proj or MLP bias, none under QK-norm).
@@ -198,6 +219,59 @@ static int parse_config(const char* json, ModelConfig* c) {
   }
   if (!c->hidden || !c->vocab || !c->layers || !c->nh)
     return set_err(5, "config.json: missing required fields");
+  if (c->fused_ckpt && c->fp8)
+    return set_err(5, "config.json: quant_method fp8 with model_type phi3 is "
+                      "not supported");
+  // partial rotary: top-level (the on-disk form) or inside rope_parameters
+  auto rp = v->get("rope_parameters");
+  if (rp && rp->kind != minijson::Value::Obj) rp = nullptr;
+  {
+    auto p = v->get("partial_rotary_factor");
+    if (!p && rp) p = rp->get("partial_rotary_factor");
+    if (p && p->kind == minijson::Value::Num)
+      c->rotary_factor = (float)p->num;
+  }
+  const int hd = c->hd(), rd = c->rd();
+  if (rd != hd && (rd <= 0 || rd > hd || rd % 4 != 0 || (hd - rd) % 4 != 0))
+    return set_err(5, "config.json: partial_rotary_factor %g gives %d rotary "
+                      "dims of head_dim %d; both they and the rest must be "
+                      "positive multiples of 4", (double)c->rotary_factor, rd,
+                   hd);
+  if (rd < hd && (c->qk_norm || c->qkv_bias))
+    return set_err(5, "config.json: partial_rotary_factor %g together with "
+                      "%s is not supported", (double)c->rotary_factor,
+                   c->qk_norm ? "QK-norm" : "the qwen2 q/k/v bias");
+  // LongRoPE, under rope_scaling or rope_parameters
+  for (auto rs : {v->get("rope_scaling"), rp}) {
+    if (!rs || rs->kind != minijson::Value::Obj) continue;
+    auto ty = rs->get("rope_type");
+    if (!ty) ty = rs->get("type");
+    if (!ty || (ty->str != "longrope" && ty->str != "su")) continue;
+    c->rope_long = true;
+    for (int which = 0; which < 2; ++which) {
+      const char* name = which ? "long_factor" : "short_factor";
+      std::vector<float>& dst = which ? c->lr_long : c->lr_short;
+      dst.clear();
+      auto a = rs->get(name);
+      if (a && a->kind == minijson::Value::Arr)
+        for (auto& x : a->arr) dst.push_back((float)x->num);
+      if ((int)dst.size() != rd / 2)
+        return set_err(5, "config.json: longrope %s has %d entries, expected "
+                          "%d (rotary dims / 2)", name, (int)dst.size(),
+                       rd / 2);
+    }
+    auto om = rs->get("original_max_position_embeddings");
+    if (!om) om = v->get("original_max_position_embeddings");
+    if (!om || om->kind != minijson::Value::Num || om->num < 2)
+      return set_err(5, "config.json: longrope needs "
+                        "original_max_position_embeddings");
+    c->lr_orig = (float)om->num;
+    if (auto p = rs->get("factor"))
+      if (p->kind == minijson::Value::Num) c->lr_factor = (float)p->num;
+    if (auto p = rs->get("attention_factor"))
+      if (p->kind == minijson::Value::Num) c->lr_attn = (float)p->num;
+    break;
+  }
   return 0;
 }
 
@@ -221,6 +295,12 @@ static int w4_dim_err(const char* name, int N, int K, int g) {
 static int w4_config_err(const ModelConfig& c) {
   const int H = c.hidden, I = c.inter, Sq = c.sq(), Skv = c.skv();
   int r;
+  if (c.fused_ckpt) {  // phi3: one packed tensor each, repacked whole
+    if ((r = w4_dim_err("qkv_proj", c.nqkv(), H, c.grp(H)))) return r;
+    if ((r = w4_dim_err("gate_up_proj", 2 * I, H, c.grp(H)))) return r;
+    if ((r = w4_dim_err("o_proj", H, Sq, c.grp(Sq)))) return r;
+    return w4_dim_err("down_proj", H, I, c.grp(I));
+  }
   if ((r = w4_dim_err("q_proj", Sq, H, c.grp(H)))) return r;
   if ((r = w4_dim_err("k_proj/v_proj", Skv, H, c.grp(H)))) return r;
   if ((r = w4_dim_err("o_proj", H, Sq, c.grp(Sq)))) return r;
@@ -236,11 +316,34 @@ static int w4_config_err(const ModelConfig& c) {
 static void build_rope_tables(const ModelConfig& c, int max_seq,
                               std::vector<float>* cos_t,
                               std::vector<float>* sin_t) {
-  int rd = c.hd();  // partial_rotary_factor = 1 for the in-scope configs
+  int rd = c.rd();  // rotated dims: hd unless partial_rotary_factor < 1
   int half = rd / 2;
   std::vector<float> theta(half);
   for (int i = 0; i < half; ++i)
     theta[i] = 1.0f / powf(c.rope_theta, (float)(2 * i) / (float)rd);
+  // LongRoPE (HF _compute_longrope_parameters): inv_freq_i =
+  // 1 / (f_i * theta^(2i/rd)) and both tables times the attention factor m.
+  // The list is chosen ONCE, by the engine's max_seq: long_factor if max_seq
+  // exceeds original_max_position_embeddings, else short_factor.  (HF chooses
+  // per forward call by the current length and drops its cache at the
+  // crossing; one preallocated cache with one table cannot.)
+  float m = 1.f;
+  if (c.rope_long) {
+    const std::vector<float>& f =
+        (float)max_seq > c.lr_orig ? c.lr_long : c.lr_short;
+    // in double, rounded once: the f32 exponent 2i/rd alone would cost
+    // ln(theta) * 2^-24 relative on the frequency
+    for (int i = 0; i < half; ++i)
+      theta[i] = (float)(1.0 / ((double)f[i] * pow((double)c.rope_theta,
+                                                   2.0 * i / (double)rd)));
+    if (c.lr_attn > 0) {
+      m = c.lr_attn;
+    } else {
+      const float s =
+          c.lr_factor > 0 ? c.lr_factor : (float)c.max_pos / c.lr_orig;
+      m = s <= 1.f ? 1.f : sqrtf(1.f + logf(s) / logf(c.lr_orig));
+    }
+  }
   if (c.rope_llama3 && c.rs_orig > 0) {
     float low_wl = c.rs_orig / c.rs_low;
     float high_wl = c.rs_orig / c.rs_high;
@@ -261,9 +364,26 @@ static void build_rope_tables(const ModelConfig& c, int max_seq,
   for (int p = 0; p < max_seq; ++p)
     for (int i = 0; i < half; ++i) {
       float a = (float)p * theta[i];
-      (*cos_t)[(size_t)p * half + i] = cosf(a);
-      (*sin_t)[(size_t)p * half + i] = sinf(a);
+      (*cos_t)[(size_t)p * half + i] = c.rope_long ? m * cosf(a) : cosf(a);
+      (*sin_t)[(size_t)p * half + i] = c.rope_long ? m * sinf(a) : sinf(a);
     }
+}
+
+// The tables engine create builds for this config and max_seq (host only).
+extern "C" int cake_hip_rope_tables(const char* config_json, int max_seq,
+                                    float* cosv, float* sinv, int* rd_out) {
+  ModelConfig c;
+  int r = parse_config(config_json, &c);
+  if (r) return r;
+  if (max_seq < 32 || max_seq % 32 != 0)
+    return set_err(5, "rope_tables: max_seq %d must be a positive multiple of "
+                      "32 (engine create rounds up to one)", max_seq);
+  std::vector<float> ct, st;
+  build_rope_tables(c, max_seq, &ct, &st);
+  if (cosv) memcpy(cosv, ct.data(), ct.size() * sizeof(float));
+  if (sinv) memcpy(sinv, st.data(), st.size() * sizeof(float));
+  if (rd_out) *rd_out = c.rd();
+  return 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -474,15 +594,15 @@ static void stats_flush(cake_engine* e) {
 
 // Full-rotation models without qk-norm and without fp8/4-bit weights take the
 // fused rms_norm -> qkv GEMV -> rope -> KV-store kernel (the QK-norm rows
-// exist exactly when c.qk_norm; qwen2 takes its biased twin).  Shared with
-// cake_hip_decode_dispatch.
+// exist exactly when c.qk_norm; qwen2 takes its biased twin, partial rotary
+// the _pr form).  Shared with cake_hip_decode_dispatch.
 // algorithmic bytes of one packed 4-bit tensor: nibbles + {s, -(z+1)s} pairs
 static double w4_bytes(double N, double K, double g) {
   return N * K * 0.5 + N * (K / g) * 8.0;
 }
 static bool fused_qkv_rope_applies(const ModelConfig& c) {
   return !c.fp8 && !c.w4 && !c.qk_norm && c.hd() % 4 == 0 &&
-         c.nqkv() % 4 == 0;
+         c.nqkv() % 4 == 0 && c.rd() % 4 == 0 && (c.hd() - c.rd()) % 4 == 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -497,14 +617,18 @@ static void enqueue_layer_decode(cake_engine* e, LayerDev& l,
   // Full-rotation models without qk-norm (llama family) take the fused
   // rms_norm -> qkv GEMV -> rope -> KV-store kernel: one launch instead of
   // two, with the rope applied to the dot-product sums in LDS.
+  // (CAKE_BF16_SPLITNORM sends a partial-rotary model down the split route,
+  // norm + GEMV + store: the A/B leg of k_gemv_qkv_rope_pr.  Full-rotation
+  // models keep the fused kernel under it, as before.)
   const bool fused_qkv_rope =
-      fused_qkv_rope_applies(c) && !l.qnorm && !l.knorm;
+      fused_qkv_rope_applies(c) && !l.qnorm && !l.knorm &&
+      !(e->bf16_splitnorm && c.rd() != hd);
   if (fused_qkv_rope) {
     double wb = (double)Nq * H * 2;
     StatScope ss(e, "gemv_qkv", wb + 2.0 * H * 2 + Nq * 2, 2.0 * Nq * H);
     launch_gemv_qkv_rope(l.wqkv, e->x, e->qkv, l.rms1, c.rms_eps, l.kc,
                          l.vc, l.vtc, e->cos_t, e->sin_t, e->dev_pos, c.nh,
-                         c.nkv, hd, e->max_seq, H, e->stream, l.bqkv);
+                         c.nkv, hd, c.rd(), e->max_seq, H, e->stream, l.bqkv);
   } else if (c.w4) {  // split norm -> 4-bit GEMV -> rope + KV store
     {
       StatScope ss(e, "rmsnorm", 2.0 * H * 2, 0);
@@ -518,7 +642,7 @@ static void enqueue_layer_decode(cake_engine* e, LayerDev& l,
     }
     StatScope ss(e, "rope_store", 0, 0);
     launch_rope_store_decode(e->qkv, l.kc, l.vc, l.vtc, e->cos_t, e->sin_t,
-                             e->dev_pos, c.nh, c.nkv, hd, hd, e->max_seq,
+                             e->dev_pos, c.nh, c.nkv, hd, c.rd(), e->max_seq,
                              l.qnorm, l.knorm, c.rms_eps, e->stream, l.bqkv);
   } else {
     {  // rms_1 fused into the qkv projection (GEMV, x kept in registers)
@@ -552,7 +676,7 @@ static void enqueue_layer_decode(cake_engine* e, LayerDev& l,
        // KV store
       StatScope ss(e, "rope_store", (double)Nq * hd * 0, 0);
       launch_rope_store_decode(e->qkv, l.kc, l.vc, l.vtc, e->cos_t, e->sin_t,
-                               e->dev_pos, c.nh, c.nkv, hd, hd, e->max_seq,
+                               e->dev_pos, c.nh, c.nkv, hd, c.rd(), e->max_seq,
                                l.qnorm, l.knorm, c.rms_eps, e->stream,
                                l.bqkv);
     }
@@ -689,8 +813,9 @@ static void enqueue_layer_prefill(cake_engine* e, LayerDev& l, int S,
   {  // [fused QK-norm | qkv bias +] rope + KV store for all S positions
     StatScope ss(e, "rope_store_pf", 0, 0);
     launch_rope_store_prefill(e->qkv, l.kc, l.vc, l.vtc, e->cos_t, e->sin_t,
-                              pos0, S, c.nh, c.nkv, hd, hd, e->max_seq, Nq,
-                              l.qnorm, l.knorm, c.rms_eps, e->stream, l.bqkv);
+                              pos0, S, c.nh, c.nkv, hd, c.rd(), e->max_seq,
+                              Nq, l.qnorm, l.knorm, c.rms_eps, e->stream,
+                              l.bqkv);
   }
   {
     double n_avg = pos0 + (S + 1) * 0.5;
@@ -1451,6 +1576,34 @@ static int load_safetensors_file(cake_engine* e, const char* path) {
       LOADW(pre + "mlp.up_proj.weight_scale_inv", upload_scale(e, l.sgu + Ib * Hb, base, t, Ib * Hb));
       LOADW(pre + "mlp.down_proj.weight", upload_weight_u8(e, l.wdown8, base, t, H * I));
       LOADW(pre + "mlp.down_proj.weight_scale_inv", upload_scale(e, l.sdown, base, t, Hb * Ib));
+    } else if (c.fused_ckpt) {
+      // phi3: qkv_proj (q|k|v rows) and gate_up_proj (gate rows, then up
+      // rows) are the engine's own wqkv / wgu layouts and load whole
+      // (phi4/config.rs:88-89); a checkpoint with split names fails on the
+      // fused name
+      const size_t Nq = Sq + 2 * Skv;
+      if (c.w4) {
+        const size_t gH = c.grp((int)H), gS = c.grp((int)Sq), gI = c.grp((int)I);
+        if ((r = load_w4(pre + "self_attn.qkv_proj", l.wqkv4, l.zqkv, 0, Nq, H, gH))) return r;
+        if ((r = load_w4(pre + "self_attn.o_proj", l.wo4, l.zo, 0, H, Sq, gS))) return r;
+        if ((r = load_w4(pre + "mlp.gate_up_proj", l.wgu4, l.zgu, 0, 2 * I, H, gH))) return r;
+        if ((r = load_w4(pre + "mlp.down_proj", l.wdown4, l.zdown, 0, H, I, gI))) return r;
+      } else {
+        auto fused = [&](const std::string& name, u16* dst, size_t N) -> int {
+          if (t.shape.size() != 2 || (size_t)t.shape[0] != N ||
+              (size_t)t.shape[1] != H) {
+            std::string got;
+            for (long d : t.shape) got += (got.empty() ? "" : ", ") + std::to_string(d);
+            return set_err(5, "%s: shape (%s), expected (%zu, %zu)",
+                           name.c_str(), got.c_str(), N, H);
+          }
+          return upload_weight(e, dst, base, t, N * H);
+        };
+        LOADW(pre + "self_attn.qkv_proj.weight", fused(pre + "self_attn.qkv_proj.weight", l.wqkv, Nq));
+        LOADW(pre + "self_attn.o_proj.weight", upload_weight(e, l.wo, base, t, H * Sq));
+        LOADW(pre + "mlp.gate_up_proj.weight", fused(pre + "mlp.gate_up_proj.weight", l.wgu, 2 * I));
+        LOADW(pre + "mlp.down_proj.weight", upload_weight(e, l.wdown, base, t, H * I));
+      }
     } else if (c.w4) {
       // gptq: qweight/qzeros/scales per projection, repacked out-major at
       // the projection's row offset of the fused tensor (g_idx is ignored,
@@ -2233,9 +2386,19 @@ static int attn_geom_err(const char* who, int nh, int nkv, int hd,
   return 0;
 }
 
-// shared body of cake_hip_op_kv_store[_bias]; bias may be null
+// rd of the _pr op entries: the launchers' contract
+static int op_rd_err(const char* who, int hd, int rd) {
+  if (rd == hd) return 0;
+  if (rd <= 0 || rd > hd || rd % 4 != 0 || (hd - rd) % 4 != 0)
+    return set_err(5, "%s: rd %d of hd %d: both it and the rest must be "
+                   "positive multiples of 4", who, rd, hd);
+  return 0;
+}
+
+// shared body of cake_hip_op_kv_store[_bias|_pr]; bias may be null; the
+// tables are (max_seq, rd/2)
 static int op_kv_store_impl(const char* who, int S, int pos0, int decode,
-                            int nh, int nkv, int hd, int max_seq,
+                            int nh, int nkv, int hd, int rd, int max_seq,
                             const float* qkv, const float* cosv,
                             const float* sinv, const float* q_norm,
                             const float* k_norm, float eps,
@@ -2253,12 +2416,16 @@ static int op_kv_store_impl(const char* who, int S, int pos0, int decode,
   if (bias && q_norm)
     return set_err(5, "%s: a bias together with QK-norm is not supported",
                    who);
+  if ((r = op_rd_err(who, hd, rd))) return r;
+  if (rd != hd && q_norm)
+    return set_err(5, "%s: rd < hd together with QK-norm is not supported",
+                   who);
   OpBufs b;
   HIP_TRY(hipSetDevice(device));
   HIP_TRY(hipStreamCreate(&b.s));
   const int Nq = (nh + 2 * nkv) * hd;
   const size_t ncache = (size_t)nkv * max_seq * hd;
-  const size_t ntab = (size_t)max_seq * (hd / 2);
+  const size_t ntab = (size_t)max_seq * (rd / 2);
   u16 *dqkv, *dkc, *dvc, *dvtc, *dqn = nullptr, *dkn = nullptr;
   void *dcos, *dsin, *dpos, *dbias = nullptr;
   if ((r = ob_up16(b, qkv, (size_t)S * Nq, &dqkv))) return r;
@@ -2276,11 +2443,11 @@ static int op_kv_store_impl(const char* who, int S, int pos0, int decode,
   if (decode)
     launch_rope_store_decode(dqkv, dkc, dvc, dvtc, (const float*)dcos,
                              (const float*)dsin, (const int*)dpos, nh, nkv,
-                             hd, hd, max_seq, dqn, dkn, eps, b.s,
+                             hd, rd, max_seq, dqn, dkn, eps, b.s,
                              (const float*)dbias);
   else
     launch_rope_store_prefill(dqkv, dkc, dvc, dvtc, (const float*)dcos,
-                              (const float*)dsin, pos0, S, nh, nkv, hd, hd,
+                              (const float*)dsin, pos0, S, nh, nkv, hd, rd,
                               max_seq, Nq, dqn, dkn, eps, b.s,
                               (const float*)dbias);
   HIP_TRY(hipGetLastError());
@@ -2300,7 +2467,7 @@ extern "C" int cake_hip_op_kv_store(int S, int pos0, int decode, int nh,
                                     const float* k_norm, float eps, float* kc,
                                     float* vc, float* vtc, float* q_out,
                                     int device) {
-  return op_kv_store_impl("op_kv_store", S, pos0, decode, nh, nkv, hd,
+  return op_kv_store_impl("op_kv_store", S, pos0, decode, nh, nkv, hd, hd,
                           max_seq, qkv, cosv, sinv, q_norm, k_norm, eps,
                           nullptr, kc, vc, vtc, q_out, device);
 }
@@ -2314,8 +2481,19 @@ extern "C" int cake_hip_op_kv_store_bias(int S, int pos0, int decode, int nh,
                                          float* vc, float* vtc, float* q_out,
                                          int device) {
   return op_kv_store_impl("op_kv_store_bias", S, pos0, decode, nh, nkv, hd,
-                          max_seq, qkv, cosv, sinv, q_norm, k_norm, eps, bias,
-                          kc, vc, vtc, q_out, device);
+                          hd, max_seq, qkv, cosv, sinv, q_norm, k_norm, eps,
+                          bias, kc, vc, vtc, q_out, device);
+}
+extern "C" int cake_hip_op_kv_store_pr(int S, int pos0, int decode, int nh,
+                                       int nkv, int hd, int rd, int max_seq,
+                                       const float* qkv, const float* cosv,
+                                       const float* sinv, const float* q_norm,
+                                       const float* k_norm, float eps,
+                                       float* kc, float* vc, float* vtc,
+                                       float* q_out, int device) {
+  return op_kv_store_impl("op_kv_store_pr", S, pos0, decode, nh, nkv, hd, rd,
+                          max_seq, qkv, cosv, sinv, q_norm, k_norm, eps,
+                          nullptr, kc, vc, vtc, q_out, device);
 }
 
 extern "C" int cake_hip_op_attn_prefill(int S, int pos0, int nh, int nkv,
@@ -2699,10 +2877,11 @@ extern "C" int cake_hip_op_gemv_gateup(int fp8, int I, int K, int rows,
   return ob_down16(b, dout, (size_t)I + OPG, out);
 }
 
-// shared body of cake_hip_op_gemv_qkv_rope[_bias]; bias may be null
+// shared body of cake_hip_op_gemv_qkv_rope[_bias|_pr]; bias may be null; the
+// tables are (max_seq, rd/2)
 static int op_gemv_qkv_rope_impl(const char* who, int nh, int nkv, int hd,
-                                 int max_seq, int pos, int K, const float* x,
-                                 const float* nw, float eps, const float* w,
+                                 int rd, int max_seq, int pos, int K,
+                                 const float* x, const float* nw, float eps, const float* w,
                                  const float* cosv, const float* sinv,
                                  const float* bias, float* kc, float* vc,
                                  float* vtc, float* out, int device) {
@@ -2716,12 +2895,13 @@ static int op_gemv_qkv_rope_impl(const char* who, int nh, int nkv, int hd,
                    K);
   if (!x || !nw || !w || !out)
     return set_err(5, "%s: x, nw, w and out are required", who);
+  if ((r = op_rd_err(who, hd, rd))) return r;
   OpBufs b;
   HIP_TRY(hipSetDevice(device));
   HIP_TRY(hipStreamCreate(&b.s));
   const int Nq = (nh + 2 * nkv) * hd;
   const size_t ncache = (size_t)nkv * max_seq * hd;
-  const size_t ntab = (size_t)max_seq * (hd / 2);
+  const size_t ntab = (size_t)max_seq * (rd / 2);
   u16 *dx, *dnw, *dw, *dkc, *dvc, *dvtc, *dout;
   void *dcos, *dsin, *dpos, *dbias = nullptr;
   if ((r = ob_up16(b, x, K, &dx))) return r;
@@ -2738,7 +2918,7 @@ static int op_gemv_qkv_rope_impl(const char* who, int nh, int nkv, int hd,
   if ((r = ob_sent16(b, (size_t)Nq + OPG, &dout))) return r;
   launch_gemv_qkv_rope(dw, dx, dout, dnw, eps, dkc, dvc, dvtc,
                        (const float*)dcos, (const float*)dsin,
-                       (const int*)dpos, nh, nkv, hd, max_seq, K, b.s,
+                       (const int*)dpos, nh, nkv, hd, rd, max_seq, K, b.s,
                        (const float*)dbias);
   HIP_TRY(hipGetLastError());
   if ((r = ob_down16(b, dout, (size_t)Nq + OPG, out))) return r;
@@ -2753,8 +2933,8 @@ extern "C" int cake_hip_op_gemv_qkv_rope(int nh, int nkv, int hd, int max_seq,
                                          const float* sinv, float* kc,
                                          float* vc, float* vtc, float* out,
                                          int device) {
-  return op_gemv_qkv_rope_impl("op_gemv_qkv_rope", nh, nkv, hd, max_seq, pos,
-                               K, x, nw, eps, w, cosv, sinv, nullptr, kc, vc,
+  return op_gemv_qkv_rope_impl("op_gemv_qkv_rope", nh, nkv, hd, hd, max_seq,
+                               pos, K, x, nw, eps, w, cosv, sinv, nullptr, kc, vc,
                                vtc, out, device);
 }
 extern "C" int cake_hip_op_gemv_qkv_rope_bias(
@@ -2762,9 +2942,18 @@ extern "C" int cake_hip_op_gemv_qkv_rope_bias(
     const float* nw, float eps, const float* w, const float* cosv,
     const float* sinv, const float* bias, float* kc, float* vc, float* vtc,
     float* out, int device) {
-  return op_gemv_qkv_rope_impl("op_gemv_qkv_rope_bias", nh, nkv, hd, max_seq,
-                               pos, K, x, nw, eps, w, cosv, sinv, bias, kc, vc,
-                               vtc, out, device);
+  return op_gemv_qkv_rope_impl("op_gemv_qkv_rope_bias", nh, nkv, hd, hd,
+                               max_seq, pos, K, x, nw, eps, w, cosv, sinv,
+                               bias, kc, vc, vtc, out, device);
+}
+extern "C" int cake_hip_op_gemv_qkv_rope_pr(
+    int nh, int nkv, int hd, int rd, int max_seq, int pos, int K,
+    const float* x, const float* nw, float eps, const float* w,
+    const float* cosv, const float* sinv, float* kc, float* vc, float* vtc,
+    float* out, int device) {
+  return op_gemv_qkv_rope_impl("op_gemv_qkv_rope_pr", nh, nkv, hd, rd,
+                               max_seq, pos, K, x, nw, eps, w, cosv, sinv,
+                               nullptr, kc, vc, vtc, out, device);
 }
 
 extern "C" int cake_hip_op_gemm(int variant, int M, int N, int K, int epi,

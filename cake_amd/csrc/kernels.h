@@ -44,13 +44,21 @@ void launch_gemv_res_splitk(const u16* W, const u16* x, u16* out,
 // fused rms_norm -> qkv GEMV -> rope -> KV-cache store (llama family).
 // bias: the fused q|k|v projection bias row (Nq f32, qwen2) added to the f32
 // sums; non-null runs k_gemv_qkv_rope_bias (kernels_qkv_bias.hip), null the
-// unbiased kernel.
+// unbiased kernel.  rd = rotated dims of a head: rd == hd runs these two
+// kernels, rd < hd the partial-rotary form below (which takes no bias).
 void launch_gemv_qkv_rope(const u16* W, const u16* x, u16* out, const u16* nw,
                           float eps, u16* kc, u16* vc, u16* vtc,
                           const float* cost, const float* sint,
-                          const int* pos, int nh, int nkv, int hd,
+                          const int* pos, int nh, int nkv, int hd, int rd,
                           int max_seq, int K, hipStream_t s,
                           const float* bias = nullptr);
+// partial rotary (rd < hd, rd % 4 == 0, (hd - rd) % 4 == 0, no bias):
+// k_gemv_qkv_rope_pr (kernels_qkv_pr.hip); tables are (max_seq, rd/2)
+void launch_gemv_qkv_rope_pr(const u16* W, const u16* x, u16* out,
+                             const u16* nw, float eps, u16* kc, u16* vc,
+                             u16* vtc, const float* cost, const float* sint,
+                             const int* pos, int nh, int nkv, int hd, int rd,
+                             int max_seq, int K, hipStream_t s);
 void launch_gemv_qkv_rope_bias(const u16* W, const u16* x, u16* out,
                                const u16* nw, float eps, u16* kc, u16* vc,
                                u16* vtc, const float* cost, const float* sint,

@@ -501,9 +501,14 @@ int gemv_fp8_rows_policy(int N) {
 void launch_gemv_qkv_rope(const u16* W, const u16* x, u16* out, const u16* nw,
                           float eps, u16* kc, u16* vc, u16* vtc,
                           const float* cost, const float* sint,
-                          const int* pos, int nh, int nkv, int hd,
+                          const int* pos, int nh, int nkv, int hd, int rd,
                           int max_seq, int K, hipStream_t s,
                           const float* bias) {
+  if (rd != hd) {  // partial rotary: its own translation unit as well
+    launch_gemv_qkv_rope_pr(W, x, out, nw, eps, kc, vc, vtc, cost, sint, pos,
+                            nh, nkv, hd, rd, max_seq, K, s);
+    return;
+  }
   if (bias) {  // qwen2: the biased twin lives in its own translation unit
     launch_gemv_qkv_rope_bias(W, x, out, nw, eps, kc, vc, vtc, cost, sint, pos,
                               bias, nh, nkv, hd, max_seq, K, s);

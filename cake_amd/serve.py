@@ -284,7 +284,9 @@ def create_app(engine, model_name="cake-amd", tokenizer=None, eos_ids=(),
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--model", default="llama3-8b")
+    ap.add_argument("--model", default="llama3-8b",
+                    help="a name from configs.MODELS, QUANT_MODELS, "
+                    "QWEN2_MODELS or PHI_MODELS (e.g. phi-4-mini)")
     ap.add_argument("--safetensors", default=None)
     ap.add_argument("--tokenizer", default=None,
                     help="path to a tokenizer.json")

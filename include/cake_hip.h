@@ -84,7 +84,28 @@ void cake_hip_engine_free(cake_engine *e);
  * dimension) in every weight format; they are kept as one fused f32 row per
  * layer, and a missing or mis-shaped one is an error that names the tensor.
  * Other model types ignore bias tensors; a config with attention_bias or
- * mlp_bias true on another model type is refused at create (error 5). */
+ * mlp_bias true on another model type is refused at create (error 5).
+ * model_type "phi3" (Phi-3, Phi-4-mini, Phi-4) reads the checkpoint's fused
+ * tensors instead of the split ones: self_attn.qkv_proj (q|k|v rows) and
+ * mlp.gate_up_proj (gate rows, then up rows), as .weight or, for gptq, as
+ * .qweight/.qzeros/.scales; a missing or mis-shaped one is an error that names
+ * it, and phi3 with fp8 is refused at create.
+ *
+ * Rotary embedding read from config_json, for any model type:
+ *  - partial_rotary_factor (top level, or inside rope_parameters; absent = 1):
+ *    rd = (int)(head_dim * factor) leading dims of each head rotate, the rest
+ *    pass through.  rd and head_dim - rd must be multiples of 4; rd < head_dim
+ *    with QK-norm or with the qwen2 bias is refused (error 5).
+ *  - rope_scaling / rope_parameters of type "llama3", or "longrope" / "su"
+ *    (short_factor and long_factor of rd/2 entries each,
+ *    original_max_position_embeddings in the dict or at top level, optional
+ *    factor and attention_factor; HF _compute_longrope_parameters).  The
+ *    LongRoPE list is chosen ONCE per engine: long_factor if the engine's
+ *    max_seq exceeds original_max_position_embeddings, else short_factor.  HF
+ *    transformers chooses per forward call by the current length and drops its
+ *    cache at the crossing, which one preallocated cache cannot do: create the
+ *    engine with max_seq <= original_max_position_embeddings to serve short
+ *    contexts with the short list.  Other scaling types are ignored. */
 int cake_hip_load_safetensors(cake_engine *e, const char *path);
 
 /* Seeded random init on device (synthetic-weights benches; no network for
@@ -188,6 +209,17 @@ int cake_hip_op_kv_store_bias(int S, int pos0, int decode, int nh, int nkv,
                               float eps, const float *bias, float *kc,
                               float *vc, float *vtc, float *q_out,
                               int device);
+/* kv_store with partial rotary: only the first rd dims of each q and k head
+ * rotate, cosv / sinv are (max_seq, rd/2); q's remaining dims stay as they
+ * are, k's are copied to the cache.  rd and hd - rd must be multiples of 4;
+ * rd < hd with q_norm/k_norm is refused.  rd == hd is op_kv_store bit for
+ * bit. */
+int cake_hip_op_kv_store_pr(int S, int pos0, int decode, int nh, int nkv,
+                            int hd, int rd, int max_seq, const float *qkv,
+                            const float *cosv, const float *sinv,
+                            const float *q_norm, const float *k_norm,
+                            float eps, float *kc, float *vc, float *vtc,
+                            float *q_out, int device);
 /* Causal [sliding-window] GQA attention of S post-rope q rows (S, nh*hd) at
  * positions pos0.. over the cache images; out (S, nh*hd).  Variant: hd 128
  * takes pfv 1 (nw 8, no split/deep) or pfv 2 with nw 4|8 and at most one of
@@ -278,6 +310,15 @@ int cake_hip_op_gemv_qkv_rope_bias(int nh, int nkv, int hd, int max_seq,
                                    const float *cosv, const float *sinv,
                                    const float *bias, float *kc, float *vc,
                                    float *vtc, float *out, int device);
+/* The same with partial rotary (tables (max_seq, rd/2)): rd < hd runs
+ * k_gemv_qkv_rope_pr, rd == hd the full-rotation kernel (op_gemv_qkv_rope bit
+ * for bit). */
+int cake_hip_op_gemv_qkv_rope_pr(int nh, int nkv, int hd, int rd, int max_seq,
+                                 int pos, int K, const float *x,
+                                 const float *nw, float eps, const float *w,
+                                 const float *cosv, const float *sinv,
+                                 float *kc, float *vc, float *vtc, float *out,
+                                 int device);
 /* C[M,N] = A[M,K] @ W[N,K]^T (+ res) by an explicit variant: 0 128^2 tile,
  * 1 256^2, 2 128x256, 3 256^2 fine-phase, 4 hipBLASLt.  Variants 1..3 need
  * K % 64 == 0 (any number of 64-wide tiles >= 1); 0 and 4 take K % 8 == 0.
@@ -365,6 +406,13 @@ int cake_hip_linear_dispatch_w4(int kind, int n, int K, int group,
  * {family, rows, KB} for i = qkv, o, gate-up, down, head.  The opt-in
  * split-K residual GEMV is not reflected. */
 int cake_hip_decode_dispatch(const char *config_json, int out[15]);
+/* Host only: the rope tables engine create builds for config_json at this
+ * max_seq (a positive multiple of 32, as create rounds it), through the same
+ * function: cosv and sinv are (max_seq, rd/2) f32 and may be NULL; *rd_out is
+ * the rotated dims per head.  Every config refusal of create that concerns
+ * the rotary fields is reported here as well (error 5). */
+int cake_hip_rope_tables(const char *config_json, int max_seq, float *cosv,
+                         float *sinv, int *rd_out);
 
 /* ---- observability (bench roofline evidence) ----------------------------
  * JSON {"kernels": {name: {"launches": n, "ms": t, "bytes": b}}} — per-
