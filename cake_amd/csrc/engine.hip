@@ -135,6 +135,32 @@ int parse_config(const char* json, ModelConfig* c) {
     if (auto qm = qc->get("quant_method")) {
       c->fp8 = qm->str == "fp8";
       c->w4 = qm->str == "gptq";
+      if (c->fp8) {
+        // the kernels and the loader's scale offsets are built for 128 x 128
+        // blocks (fp8.rs:17); absent (or null) means that default
+        auto bs = qc->get("weight_block_size");
+        if (bs && !bs->is_null()) {
+          // the value as written, for the message: a number or a list of them
+          auto show = [](const minijson::Value& x) {
+            char num[32];
+            snprintf(num, sizeof num, "%g", x.num);
+            return x.kind == minijson::Value::Num ? std::string(num)
+                                                  : std::string("?");
+          };
+          std::string shown = show(*bs);
+          if (bs->kind == minijson::Value::Arr) {
+            shown = "[";
+            for (size_t i = 0; i < bs->arr.size(); ++i)
+              shown += (i ? ", " : "") + show(*bs->arr[i]);
+            shown += "]";
+          }
+          if (shown != "[128, 128]")
+            return set_err(5, "config.json: quantization_config."
+                              "weight_block_size %s is not supported (fp8 "
+                              "weights need [128, 128] blocks)",
+                           shown.c_str());
+        }
+      }
       if (c->w4) {  // AutoGPTQ 4-bit, no act-order (gptq.rs:69-86)
         int bits = 4;
         if (auto p = qc->get("bits")) bits = (int)p->num_or(4);
