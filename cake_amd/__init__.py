@@ -71,6 +71,7 @@ def _load_lib():
     lib.cake_hip_op_attn_decode.argtypes = [c] * 8 + [fp] * 4 + [c]
     lib.cake_hip_attn_dispatch.argtypes = [c, c, c, c, ctypes.POINTER(c)]
     lib.cake_hip_attn_decode_path.argtypes = [c, c, c, c]
+    lib.cake_hip_attn_decode_group.argtypes = [c, c, c]
     lib.cake_hip_op_attn_decode_seq.argtypes = [c] * 7 + \
         [ctypes.POINTER(c)] + [fp] * 4 + [u32p, c]
     u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -279,14 +280,16 @@ def _op_kv_store(bias_entry, bias, qkv, cos, sin, kc, vc, vtc, pos0, nh, nkv,
 def op_attn_prefill(q, kc, vc, vtc, pos0, window=0, variant=None, device=0):
     """Prefill attention of post-rope q (S, nh, hd) at positions pos0.. over
     cache images kc/vc (nkv, max_seq, hd), vtc (nkv, hd, max_seq).  variant =
-    (pfv, nw, split, deep); default: plain v2 NW=8 at hd 128, else the
+    (pfv, nw, split, deep); default: plain v2 NW=8 at hd 128, the MFMA-256
+    kernel (1, 4, 0, 0) at hd 256 (its plain kernel is (0, 0, 0, 0)), else the
     generic kernel.  Returns (S, nh*hd)."""
     q = np.ascontiguousarray(q, dtype=np.float32)
     S, nh, hd = q.shape
     kc = np.ascontiguousarray(kc, dtype=np.float32)
     nkv, max_seq = kc.shape[0], kc.shape[1]
     if variant is None:
-        variant = (2, 8, 0, 0) if hd == 128 else (0, 0, 0, 0)
+        variant = ((2, 8, 0, 0) if hd == 128 else
+                   (1, 4, 0, 0) if hd == 256 else (0, 0, 0, 0))
     pfv, nw, split, deep = variant
     _, qp = _f32_shaped(q, (S, nh, hd), "q")
     _, kp = _f32_shaped(kc, (nkv, max_seq, hd), "kc")
@@ -350,8 +353,16 @@ def attn_decode_path(nh, nkv, hd, nchunk):
     """The decode-attention kernel the product launches for this geometry and
     chunk count (host only): 0 per-head, 1 grouped, 2 short-context (the
     default at nchunk 4).  The library reads CAKE_ATTN_SHORT on every call:
-    0 = never the short kernel, 2 = also at nchunk 8."""
+    0 = never the short kernel, 2 = also at nchunk 8.  hd 256: 3."""
     return _lib.cake_hip_attn_decode_path(nh, nkv, hd, nchunk)
+
+
+def attn_decode_group(nh, nkv, hd):
+    """q-heads per block of the decode-attention kernel at this geometry
+    (host only).  hd 256: the largest of 4, 3, 2, 1 dividing nh / nkv, capped
+    by CAKE_ATTN256_GB, which the library reads on every call (default 1: the
+    per-head route measured faster; 2..4 opt in to grouping)."""
+    return _lib.cake_hip_attn_decode_group(nh, nkv, hd)
 
 
 def op_attn_decode_seq(q, kc, vc, pos, nchunks, window=0, device=0):

@@ -107,6 +107,23 @@ PHI_4_GPTQ = dict(PHI_4,
     quantization_config=dict(quant_method="gptq", bits=4, group_size=128,
                              desc_act=False, sym=True))
 
+# Falcon3 (falcon3/, HF model_type "llama"): a plain llama-shaped model with
+# 256-wide heads and four kv heads (G = 2 in 1B, 3 in the others).  Shapes as
+# published, written down from memory: nothing here could check them against
+# the checkpoints' config.json, which a real run reads anyway.
+_FALCON3 = dict(
+    model_type="llama", head_dim=256, num_key_value_heads=4,
+    vocab_size=131072, rms_norm_eps=1e-6, rope_theta=1000042.0,
+    max_position_embeddings=32768, tie_word_embeddings=False)
+
+FALCON3_1B = dict(_FALCON3, hidden_size=2048, intermediate_size=8192,
+                  num_hidden_layers=18, num_attention_heads=8)
+FALCON3_3B = dict(_FALCON3, hidden_size=3072, intermediate_size=9216,
+                  num_hidden_layers=22, num_attention_heads=12)
+FALCON3_7B = dict(_FALCON3, hidden_size=3072, intermediate_size=23040,
+                  num_hidden_layers=28, num_attention_heads=12)
+FALCON3_10B = dict(FALCON3_7B, num_hidden_layers=40)
+
 MODELS = {
     "llama3-8b": LLAMA3_8B,
     "llama3-70b": LLAMA3_70B,
@@ -140,10 +157,20 @@ PHI_MODELS = {
 }
 
 
+# the falcon3 family (head_dim 256)
+FALCON3_MODELS = {
+    "falcon3-1b": FALCON3_1B,
+    "falcon3-3b": FALCON3_3B,
+    "falcon3-7b": FALCON3_7B,
+    "falcon3-10b": FALCON3_10B,
+}
+
+
 def find_model(name: str) -> dict:
-    """The config called `name` in MODELS, QUANT_MODELS, QWEN2_MODELS or
-    PHI_MODELS."""
-    for table in (MODELS, QUANT_MODELS, QWEN2_MODELS, PHI_MODELS):
+    """The config called `name` in MODELS, QUANT_MODELS, QWEN2_MODELS,
+    PHI_MODELS or FALCON3_MODELS."""
+    for table in (MODELS, QUANT_MODELS, QWEN2_MODELS, PHI_MODELS,
+                  FALCON3_MODELS):
         if name in table:
             return table[name]
     raise KeyError(name)

@@ -731,9 +731,9 @@ static int engine_build(const char* config_json, int layer_lo, int layer_hi,
   if (layer_lo < 0 || layer_hi > c.layers || layer_lo >= layer_hi)
     return set_err(5, "bad layer range [%d,%d) of %d", layer_lo, layer_hi,
                    c.layers);
-  if (c.hd() > 128 || c.hd() % 8 != 0)
-    return set_err(5, "head_dim %d unsupported (must be <=128, mult of 8)",
-                   c.hd());
+  if (c.hd() != 256 && (c.hd() < 8 || c.hd() > 128 || c.hd() % 8 != 0))
+    return set_err(5, "head_dim %d unsupported (must be a multiple of 8 in "
+                   "[8,128], or 256)", c.hd());
   if (c.hidden > 16384)
     return set_err(5, "hidden_size %d unsupported (> 16384)", c.hidden);
   if (c.hidden % 8 || c.inter % 8)

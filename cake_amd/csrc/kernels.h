@@ -133,10 +133,27 @@ void launch_attn_decode(const u16* q, const u16* kc, const u16* vc,
                         hipStream_t s);
 // grid_y of the GQA-grouped decode-attention kernel for this head geometry
 // (0 = per-head fallback kernel); the engine's chunk-count policy uses it.
+// hd 256: nh / attn256_group(nh, nkv), never 0.
 int attn_decode_grid_y(int nh, int nkv, int hd);
 // which kernel launch_attn_decode runs for (geometry, nchunk): 0 per-head,
-// 1 grouped, 2 short-context in-block split-KV (CAKE_ATTN_SHORT=0 -> 1)
+// 1 grouped, 2 short-context in-block split-KV (CAKE_ATTN_SHORT=0 -> 1),
+// 3 the hd-256 kernel (kernels_attn256.hip)
 int attn_decode_path(int nh, int nkv, int hd, int nchunk);
+// hd 256 (kernels_attn256.hip).  attn256_group: q-heads per block of
+// k_attn_decode_256, the largest of 4|3|2|1 dividing nh / nkv, capped by
+// CAKE_ATTN256_GB (read per call; default 1 = per head, the faster route).  Same ws / cnt contract as
+// launch_attn_decode, except that the elected block zeroes its cnt word.
+int attn256_group(int nh, int nkv);
+void launch_attn_decode_256(const u16* q, const u16* kc, const u16* vc,
+                            const int* pos, float* ws, u32* cnt, u16* out,
+                            int nh, int nkv, int max_seq, int nchunk,
+                            int window, hipStream_t s);
+// mfma != 0: k_attn_prefill_mfma_256 (reads vtc), else k_attn_prefill_256
+void launch_attn_prefill_256(const u16* qkv, const u16* kc, const u16* vc,
+                             const u16* vtc, u16* out, int S, int pos0,
+                             int nh, int nkv, int max_seq, int qkv_stride,
+                             int out_stride, int window, int mfma,
+                             hipStream_t s);
 // ws: split-KV partial workspace (nh * S * 2 * 132 f32) or nullptr to
 // force the single-pass path
 void launch_attn_prefill(const u16* qkv, const u16* kc, const u16* vc,
@@ -146,8 +163,9 @@ void launch_attn_prefill(const u16* qkv, const u16* kc, const u16* vc,
 // Prefill-attention variant for hd == 128: pfv 1 = per-wave MFMA kernel,
 // >= 2 = LDS-staged kernel with nw (4|8) waves per block, optional split-KV
 // (+ combine pass, only when ws != nullptr and S >= split_min_s) or a deep
-// schedule (1|2, ignored under split).  Other head dims always run the
-// generic kernel.
+// schedule (1|2, ignored under split).  hd 256: {pfv 1, nw 4} = the MFMA-256
+// kernel, {pfv 0, nw 0} = the plain hd-256 kernel.  Other head dims always
+// run the generic kernel.
 struct PfVariant {
   int pfv = 2, nw = 8, split = 0, deep = 0, split_min_s = 1024;
 };

@@ -1191,6 +1191,8 @@ __global__ __launch_bounds__(1024) void k_attn_decode_short(
 // kernel applies to this head geometry, 0 = fall back to the per-head
 // kernel.  The engine uses this for its split-KV chunk-count policy.
 int attn_decode_grid_y(int nh, int nkv, int hd) {
+  if (hd == 256 && nkv > 0 && nh > 0 && nh % nkv == 0)
+    return nh / attn256_group(nh, nkv);
   if (hd != 128 || nkv <= 0 || nh % nkv != 0) return 0;
   if (getenv("CAKE_ATTN_V2") && atoi(getenv("CAKE_ATTN_V2")) == 0) return 0;
   const int G = nh / nkv;
@@ -1208,6 +1210,7 @@ int attn_decode_grid_y(int nh, int nkv, int hd) {
 // CAKE_ATTN_SHORT=2.  CAKE_ATTN_SHORT=0 restores the grouped routing
 // everywhere.  The knob is read per launch so a test can flip it.
 int attn_decode_path(int nh, int nkv, int hd, int nchunk) {
+  if (hd == 256) return 3;
   if (attn_decode_grid_y(nh, nkv, hd) <= 0) return 0;
   const char* e = getenv("CAKE_ATTN_SHORT");
   const int mode = e ? atoi(e) : 1;
@@ -1716,6 +1719,11 @@ void launch_attn_decode(const u16* q, const u16* kc, const u16* vc,
                         const int* pos, float* ws, u32* cnt, u16* out, int nh,
                         int nkv, int hd, int max_seq, int nchunk, int window,
                         hipStream_t s) {
+  if (hd == 256) {
+    launch_attn_decode_256(q, kc, vc, pos, ws, cnt, out, nh, nkv, max_seq,
+                           nchunk, window, s);
+    return;
+  }
   const int gy = attn_decode_grid_y(nh, nkv, hd);
   if (attn_decode_path(nh, nkv, hd, nchunk) == 2) {
     // tile image per chunk + scores[16][64] + q f32 [HPB][128] + partial
@@ -1786,7 +1794,12 @@ PfVariant attn_prefill_policy(int S, int nh, int hd) {
       getenv("CAKE_PF_SPLIT") ? atoi(getenv("CAKE_PF_SPLIT")) : 0;
   static const int deep_env =
       getenv("CAKE_PF_DEEP") ? atoi(getenv("CAKE_PF_DEEP")) : 0;
-  (void)hd;
+  if (hd == 256) {  // MFMA-256 (v1 structure, 4 waves) or the plain kernel
+    PfVariant v256;
+    v256.pfv = pfv == 0 ? 0 : 1;
+    v256.nw = pfv == 0 ? 0 : 4;
+    return v256;
+  }
   // 128-row blocks whenever the 256-row grid can't give the scheduler
   // >= 2 blocks/CU of backfill against the causal work skew
   const bool nw4 = nw_env ? nw_env == 4
@@ -1817,6 +1830,11 @@ void launch_attn_prefill_variant(const u16* qkv, const u16* kc,
                                  int out_stride, int window, PfVariant v,
                                  hipStream_t s) {
   const int pfv = v.pfv;
+  if (hd == 256) {
+    launch_attn_prefill_256(qkv, kc, vc, vtc, out, S, pos0, nh, nkv, max_seq,
+                            qkv_stride, out_stride, window, pfv != 0, s);
+    return;
+  }
   if (hd == 128 && pfv >= 2) {
     const size_t smem2 = 2 * 32 * 256 + 2 * 128 * 64;
     const size_t smem3 = 3 * 32 * 256 + 3 * 128 * 64;

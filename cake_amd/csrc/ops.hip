@@ -154,9 +154,9 @@ static int attn_geom_err(const char* who, int nh, int nkv, int hd,
   if (nh <= 0 || nkv <= 0 || nh % nkv != 0)
     return set_err(5, "%s: nh %d must be a positive multiple of nkv %d", who,
                    nh, nkv);
-  if (hd < 8 || hd > 128 || hd % 8 != 0)
-    return set_err(5, "%s: hd %d must be a multiple of 8 in [8,128]", who,
-                   hd);
+  if (hd != 256 && (hd < 8 || hd > 128 || hd % 8 != 0))
+    return set_err(5, "%s: hd %d must be a multiple of 8 in [8,128], or 256",
+                   who, hd);
   if (max_seq < 32 || max_seq % 32 != 0)
     return set_err(5, "%s: max_seq %d must be a positive multiple of 32",
                    who, max_seq);
@@ -287,8 +287,11 @@ extern "C" int cake_hip_op_attn_prefill(int S, int pos0, int nh, int nkv,
                    who, pos0, pos0, S, max_seq);
   if (window < 0) return set_err(5, "%s: window %d < 0", who, window);
   // what the dispatcher can express: hd 128 -> v1, or v2 with 4|8 waves and
-  // at most one of split / deep; any other hd -> the generic kernel only
+  // at most one of split / deep; hd 256 -> the MFMA-256 kernel {1, 4} or the
+  // plain one {0, 0}; any other hd -> the generic kernel only
   const bool ok =
+      hd == 256 ? (!split && !deep &&
+                   ((pfv == 1 && nw == 4) || (pfv == 0 && nw == 0))) :
       hd == 128 ? ((pfv == 1 && nw == 8 && !split && !deep) ||
                    (pfv == 2 && (nw == 4 || nw == 8) &&
                     (split == 0 || split == 1) && deep >= 0 && deep <= 2 &&
@@ -383,6 +386,16 @@ extern "C" int cake_hip_attn_dispatch(int S, int nh, int nkv, int hd,
 
 extern "C" int cake_hip_attn_decode_path(int nh, int nkv, int hd, int nchunk) {
   return attn_decode_path(nh, nkv, hd, nchunk);
+}
+
+// q-heads per block of the decode-attention kernel at this geometry (host
+// only): hd 256 -> attn256_group under CAKE_ATTN256_GB; hd 128 -> the grouped
+// kernel's 4|2|1; anything else, or a per-head route, 1.
+extern "C" int cake_hip_attn_decode_group(int nh, int nkv, int hd) {
+  if (nh <= 0 || nkv <= 0 || nh % nkv != 0) return 1;
+  if (hd == 256) return attn256_group(nh, nkv);
+  const int gy = attn_decode_grid_y(nh, nkv, hd);
+  return gy > 0 ? nh / gy : 1;
 }
 
 extern "C" int cake_hip_op_attn_decode_seq(

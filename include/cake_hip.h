@@ -90,6 +90,9 @@ void cake_hip_engine_free(cake_engine *e);
  * mlp.gate_up_proj (gate rows, then up rows), as .weight or, for gptq, as
  * .qweight/.qzeros/.scales; a missing or mis-shaped one is an error that names
  * it, and phi3 with fp8 is refused at create.
+ * head_dim (or hidden_size / num_attention_heads) must be a multiple of 8 in
+ * [8, 128], or exactly 256 (Falcon3); anything else is refused at create
+ * (error 5) ahead of any device call.
  *
  * Rotary embedding read from config_json, for any model type:
  *  - partial_rotary_factor (top level, or inside rope_parameters; absent = 1):
@@ -183,7 +186,8 @@ int cake_hip_op_rope(int b, int h, int s, int d, const float *x,
 /* Attention + KV-store op entries (test-only).  Every call allocates
  * buffers of exactly the engine's sizes, runs the real launch wrappers on a
  * private stream and frees the buffers.  Arguments are validated before any
- * device call (error 5): nh % nkv == 0; hd % 8 == 0, 8 <= hd <= 128;
+ * device call (error 5): nh % nkv == 0; hd % 8 == 0 and 8 <= hd <= 128, or
+ * hd == 256;
  * max_seq % 32 == 0; pos0 + S <= max_seq; 1 <= nchunk <= 64; the variant
  * must be one the prefill dispatcher can express.
  *
@@ -223,8 +227,9 @@ int cake_hip_op_kv_store_pr(int S, int pos0, int decode, int nh, int nkv,
 /* Causal [sliding-window] GQA attention of S post-rope q rows (S, nh*hd) at
  * positions pos0.. over the cache images; out (S, nh*hd).  Variant: hd 128
  * takes pfv 1 (nw 8, no split/deep) or pfv 2 with nw 4|8 and at most one of
- * split (0|1) / deep (0|1|2); any other hd takes {0,0,0,0} (generic
- * kernel). */
+ * split (0|1) / deep (0|1|2); hd 256 takes {1,4,0,0} (the MFMA-256 kernel)
+ * or {0,0,0,0} (the plain hd-256 kernel); any other hd takes {0,0,0,0}
+ * (generic kernel). */
 int cake_hip_op_attn_prefill(int S, int pos0, int nh, int nkv, int hd,
                              int max_seq, int window, int pfv, int nw,
                              int split, int deep, const float *q,
@@ -243,9 +248,15 @@ int cake_hip_op_attn_decode(int nh, int nkv, int hd, int max_seq, int pos,
 int cake_hip_attn_dispatch(int S, int nh, int nkv, int hd, int out[6]);
 /* Host only: the decode-attention kernel the product launches for this head
  * geometry and chunk count: 0 = per-head, 1 = grouped, 2 = short-context
- * (all chunks of a head in one workgroup; nchunk 4).  CAKE_ATTN_SHORT, read on
- * every call: 0 = never the short kernel, 2 = also at nchunk 8. */
+ * (all chunks of a head in one workgroup; nchunk 4), 3 = the hd-256 kernel.
+ * CAKE_ATTN_SHORT, read on every call: 0 = never the short kernel, 2 = also
+ * at nchunk 8. */
 int cake_hip_attn_decode_path(int nh, int nkv, int hd, int nchunk);
+/* Host only: q-heads served by one block of the decode-attention kernel at
+ * this geometry.  hd 256: the largest of 4, 3, 2, 1 that divides nh / nkv,
+ * capped by CAKE_ATTN256_GB (read on every call).  The cap defaults to 1 (per
+ * head), which measured faster; 2..4 opt in to the grouped kernel. */
+int cake_hip_attn_decode_group(int nh, int nkv, int hd);
 /* cake_hip_op_attn_decode with a chunk count PER LAUNCH: nlaunch (1..16)
  * launches back to back on one set of buffers, launch i split over
  * nchunks[i]; out is (nlaunch, nh*hd).  cnt_out (nh words, may be NULL)
