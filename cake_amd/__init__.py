@@ -117,6 +117,15 @@ def _load_lib():
                                        u32p, fp, i32p, u32p,
                                        ctypes.POINTER(c), c]
     lib.cake_hip_op_embed.argtypes = [c, c, c, c, fp, u32p, f, fp, fp, c]
+    lib.cake_hip_rope_tables_ex.argtypes = [cp, c, c, fp, fp,
+                                            ctypes.POINTER(c)]
+    lib.cake_hip_layer_dispatch.argtypes = [cp, c, ctypes.POINTER(c),
+                                            ctypes.POINTER(c), fp]
+    lib.cake_hip_op_postnorm_add.argtypes = [c, c, f, fp, fp, fp, fp, c]
+    lib.cake_hip_op_gemv_gateup_gelu.argtypes = [c, c, c, fp, fp, fp, f, fp,
+                                                 c]
+    lib.cake_hip_op_gelu_mul_rows.argtypes = [c, c, fp, fp, c]
+    lib.cake_hip_op_embed_scaled.argtypes = [c, c, c, c, fp, u32p, fp, c]
     lib.cake_hip_sync.argtypes = [p]
     return lib
 
@@ -394,6 +403,8 @@ GEMM_VARIANTS = {"128": 0, "256": 1, "128x256": 2, "256p": 3, "library": 4}
 LINEAR_FAMILIES = ("gemv_reg", "gemv_stream", "gemv_fp8", "gemv_fp8_stream",
                    "gateup", "gateup_fp8", "qkv_rope", "splitk", "gemm",
                    "gemv_w4", "gateup_w4")
+# families past the table above (CAKE_HIP_FAM_GATEUP_GELU = 11, gemma3)
+GEMMA3_FAMILIES = ("gateup_gelu",)
 LINEAR_KINDS = {"plain": 0, "gateup": 1, "qkv_rope": 2, "splitk": 3,
                 "gemm": 4}
 
@@ -762,28 +773,109 @@ def decode_dispatch(config):
         config = json.dumps(config)
     o = (ctypes.c_int * 15)()
     _check(_lib.cake_hip_decode_dispatch(config.encode(), o))
-    return {k: (LINEAR_FAMILIES[o[3 * i]], o[3 * i + 1], o[3 * i + 2])
+    fams = LINEAR_FAMILIES + GEMMA3_FAMILIES
+    return {k: (fams[o[3 * i]], o[3 * i + 1], o[3 * i + 2])
             for i, k in enumerate(("qkv", "o", "gateup", "down", "head"))}
 
 
-def rope_tables(config, max_seq):
+def rope_tables(config, max_seq, local=False):
     """The rope tables engine create builds for this config and max_seq (host
     only, same function): (cos, sin), each (max_seq, rd/2) f32, rd the rotated
     dims of a head (partial_rotary_factor); LongRoPE's list choice and
-    attention factor included."""
+    attention factor included.  local=True: the table of a gemma3 config's
+    local (sliding) layers; the default is its global layers' table."""
     if isinstance(config, dict):
         config = json.dumps(config)
     rd = ctypes.c_int(0)
-    _check(_lib.cake_hip_rope_tables(config.encode(), max_seq, None, None,
-                                     ctypes.byref(rd)))
+    which = 1 if local else 0
+    _check(_lib.cake_hip_rope_tables_ex(config.encode(), max_seq, which, None,
+                                        None, ctypes.byref(rd)))
     cos = np.empty((max_seq, rd.value // 2), dtype=np.float32)
     sin = np.empty_like(cos)
     fpt = ctypes.POINTER(ctypes.c_float)
-    _check(_lib.cake_hip_rope_tables(config.encode(), max_seq,
-                                     cos.ctypes.data_as(fpt),
-                                     sin.ctypes.data_as(fpt),
-                                     ctypes.byref(rd)))
+    _check(_lib.cake_hip_rope_tables_ex(config.encode(), max_seq, which,
+                                        cos.ctypes.data_as(fpt),
+                                        sin.ctypes.data_as(fpt),
+                                        ctypes.byref(rd)))
     return cos, sin
+
+
+def layer_dispatch(config, layer):
+    """What engine create plans for one layer of a model (host only):
+    dict(window (0 = full attention), rope_table ("global" | "local": which
+    of a gemma3 config's two tables), q_scale (the factor folded into the
+    q-norm row: sqrt(head_dim / query_pre_attn_scalar) for gemma3, else 1))."""
+    if isinstance(config, dict):
+        config = json.dumps(config)
+    win, tab, qs = ctypes.c_int(), ctypes.c_int(), ctypes.c_float()
+    _check(_lib.cake_hip_layer_dispatch(config.encode(), int(layer),
+                                        ctypes.byref(win), ctypes.byref(tab),
+                                        ctypes.byref(qs)))
+    return dict(window=win.value, rope_table=("global", "local")[tab.value],
+                q_scale=np.float32(qs.value))
+
+
+# ---- gemma3 op entries ------------------------------------------------------
+def op_postnorm_add(x, t, w, eps=1e-6, device=0):
+    """x (S, H) + rms_norm(t) * w with HF's bf16 rounding points (the normed
+    value, then the sum); S == 1 runs the decode launch.  Returns (out (S, H),
+    guards)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    S, H = x.shape
+    _, xp = _f32_shaped(x, (S, H), "x")
+    _t, tp = _f32_shaped(t, (S, H), "t")
+    _w, wp = _f32_shaped(w, (H,), "w")
+    out = np.empty(S * H + OP_GUARD, dtype=np.float32)
+    _check(_lib.cake_hip_op_postnorm_add(
+        S, H, eps, xp, tp, wp,
+        out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), device))
+    return out[:S * H].reshape(S, H), out[S * H:]
+
+
+def op_gemv_gateup_gelu(x, w, I, nw=None, eps=1e-6, rows=0, device=0):
+    """op_gemv_gateup's bf16 form with the GELU-tanh gate.  Returns (out (I,),
+    guards)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    K = x.shape[0]
+    _, xp = _f32_shaped(x, (K,), "x")
+    _w, wp = _f32_shaped(w, (2 * I, K), "w")
+    _n, nwp = _opt_f32(nw, (K,), "nw")
+    out = np.empty(I + OP_GUARD, dtype=np.float32)
+    _check(_lib.cake_hip_op_gemv_gateup_gelu(
+        I, K, rows, xp, wp, nwp, eps,
+        out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), device))
+    return out[:I], out[I:]
+
+
+def op_gelu_mul_rows(gu, device=0):
+    """Prefill gelu_mul on gu (S, 2I) = [gate | up].  Returns (out (S, I),
+    guards)."""
+    gu = np.ascontiguousarray(gu, dtype=np.float32)
+    S, I = gu.shape[0], gu.shape[1] // 2
+    _, gp = _f32_shaped(gu, (S, 2 * I), "gu")
+    out = np.empty(S * I + OP_GUARD, dtype=np.float32)
+    _check(_lib.cake_hip_op_gelu_mul_rows(
+        S, I, gp, out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), device))
+    return out[:S * I].reshape(S, I), out[S * I:]
+
+
+def op_embed_scaled(table, ids, mode="rows", device=0):
+    """The gemma3 embedding gathers (rows times bf16(sqrt(H)), rounded to
+    bf16) on table (Vt, H); mode "rows" or "token".  Returns (out (S, H),
+    guards)."""
+    table = np.ascontiguousarray(table, dtype=np.float32)
+    if table.ndim != 2:
+        raise ValueError(f"table: shape {table.shape}, expected (Vt, H)")
+    Vt, H = table.shape
+    _, tp = _f32_shaped(table, (Vt, H), "table")
+    ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+    S = ids.size
+    out = np.empty(S * H + OP_GUARD, dtype=np.float32)
+    _check(_lib.cake_hip_op_embed_scaled(
+        Vt, H, S, {"rows": 0, "token": 1}[mode], tp,
+        ids.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+        out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), device))
+    return out[:S * H].reshape(S, H), out[S * H:]
 
 
 def comm_id() -> bytes:
@@ -801,6 +893,11 @@ class Engine:
         if isinstance(config, dict):
             config = json.dumps(config)
         cfg = json.loads(config)
+        if cfg.get("model_type") == "gemma3":
+            # the multimodal form: the text model's fields, HF's defaults
+            # for what it leaves out
+            cfg = {"num_hidden_layers": 26, "vocab_size": 262208,
+                   "hidden_size": 2304, **(cfg.get("text_config") or {})}
         if layer_hi is None:
             layer_hi = cfg["num_hidden_layers"]
         if flags is None:

@@ -124,6 +124,36 @@ FALCON3_7B = dict(_FALCON3, hidden_size=3072, intermediate_size=23040,
                   num_hidden_layers=28, num_attention_heads=12)
 FALCON3_10B = dict(FALCON3_7B, num_hidden_layers=40)
 
+# Gemma 3 text models (gemma3/, HF model_type "gemma3_text"): four (1 + w)
+# norms per layer, QK-norm, GELU-tanh gate, scaled embedding, tied head, five
+# local (sliding-window, rope base 1e4) layers to one global (rope base 1e6,
+# linear factor 8 from 4B up).  Shapes as published, written down from memory
+# like Falcon3's: no config file was at hand to check them against, and a real
+# run reads the checkpoint's config.json anyway.
+_GEMMA3 = dict(
+    model_type="gemma3_text", head_dim=256, vocab_size=262208,
+    rms_norm_eps=1e-6, rope_theta=1000000.0, rope_local_base_freq=10000.0,
+    sliding_window=1024, sliding_window_pattern=6, query_pre_attn_scalar=256,
+    hidden_activation="gelu_pytorch_tanh", max_position_embeddings=131072,
+    rope_scaling=dict(rope_type="linear", factor=8.0),
+    tie_word_embeddings=True)
+
+GEMMA3_1B = dict(_GEMMA3, hidden_size=1152, intermediate_size=6912,
+                 num_hidden_layers=26, num_attention_heads=4,
+                 num_key_value_heads=1, vocab_size=262144,
+                 sliding_window=512, max_position_embeddings=32768,
+                 rope_scaling=None)
+GEMMA3_4B = dict(_GEMMA3, hidden_size=2560, intermediate_size=10240,
+                 num_hidden_layers=34, num_attention_heads=8,
+                 num_key_value_heads=4)
+GEMMA3_12B = dict(_GEMMA3, hidden_size=3840, intermediate_size=15360,
+                  num_hidden_layers=48, num_attention_heads=16,
+                  num_key_value_heads=8)
+GEMMA3_27B = dict(_GEMMA3, hidden_size=5376, intermediate_size=21504,
+                  num_hidden_layers=62, num_attention_heads=32,
+                  num_key_value_heads=16, head_dim=128,
+                  query_pre_attn_scalar=168)
+
 MODELS = {
     "llama3-8b": LLAMA3_8B,
     "llama3-70b": LLAMA3_70B,
@@ -166,11 +196,20 @@ FALCON3_MODELS = {
 }
 
 
+# the gemma3 family (sandwich norms, GELU gate, local and global layers)
+GEMMA3_MODELS = {
+    "gemma-3-1b": GEMMA3_1B,
+    "gemma-3-4b": GEMMA3_4B,
+    "gemma-3-12b": GEMMA3_12B,
+    "gemma-3-27b": GEMMA3_27B,
+}
+
+
 def find_model(name: str) -> dict:
     """The config called `name` in MODELS, QUANT_MODELS, QWEN2_MODELS,
-    PHI_MODELS or FALCON3_MODELS."""
+    PHI_MODELS, FALCON3_MODELS or GEMMA3_MODELS."""
     for table in (MODELS, QUANT_MODELS, QWEN2_MODELS, PHI_MODELS,
-                  FALCON3_MODELS):
+                  FALCON3_MODELS, GEMMA3_MODELS):
         if name in table:
             return table[name]
     raise KeyError(name)
@@ -180,7 +219,10 @@ def weight_bytes(cfg: dict, lo=0, hi=None, embed=True, head=True) -> int:
     """Bytes of weights resident in HBM for this config: bf16, or for a gptq
     config the device 4-bit layout (packed nibbles + an f32 {scale, zero
     term} pair per row and group) with 16-bit embedding, head and norms.  A
-    qwen2 config adds its fused f32 q|k|v bias row per layer."""
+    qwen2 config adds its fused f32 q|k|v bias row per layer, a gemma3 config
+    (never quantized) its four norm rows and q/k norm rows per layer."""
+    if cfg.get("model_type") in ("gemma3_text", "gemma3"):
+        return weight_bytes_bf16(cfg, lo, hi, embed, head)
     q = cfg.get("quantization_config") or {}
     H, I, V = cfg["hidden_size"], cfg["intermediate_size"], cfg["vocab_size"]
     nh, nkv = cfg["num_attention_heads"], cfg["num_key_value_heads"]
@@ -207,16 +249,24 @@ def weight_bytes(cfg: dict, lo=0, hi=None, embed=True, head=True) -> int:
 
 
 def weight_bytes_bf16(cfg: dict, lo=0, hi=None, embed=True, head=True) -> int:
+    gemma3 = cfg.get("model_type") in ("gemma3_text", "gemma3")
+    if cfg.get("model_type") == "gemma3":    # the text model, HF's defaults
+        cfg = {"hidden_size": 2304, "intermediate_size": 9216,
+               "vocab_size": 262208, "num_hidden_layers": 26,
+               "num_attention_heads": 8, "num_key_value_heads": 4,
+               "head_dim": 256, **(cfg.get("text_config") or {})}
     H, I, V = cfg["hidden_size"], cfg["intermediate_size"], cfg["vocab_size"]
     nh, nkv = cfg["num_attention_heads"], cfg["num_key_value_heads"]
     hd = cfg.get("head_dim") or H // nh
     L = (hi if hi is not None else cfg["num_hidden_layers"]) - lo
     per_layer = (nh + 2 * nkv) * hd * H + H * nh * hd + 3 * I * H + 2 * H
+    if gemma3:                               # two more norm rows, q/k norm
+        per_layer += 2 * H + 2 * hd
     total = L * per_layer
     if embed:
         total += V * H
     if head:
         total += H
-        if not cfg.get("tie_word_embeddings"):
+        if not (gemma3 or cfg.get("tie_word_embeddings")):
             total += V * H
     return total * 2

@@ -65,6 +65,100 @@ extern "C" const char* cake_hip_last_error(void) { return g_err.c_str(); }
 // ---------------------------------------------------------------------------
 // model config parse (the struct is in engine_internal.h)
 // ---------------------------------------------------------------------------
+// The gemma3-only fields of the text config object v (HF Gemma3TextConfig):
+// what the family always sets, the layer kinds, both ropes, the score scale,
+// and the refusals.
+static int parse_gemma3(const minijson::Value& v, ModelConfig* c) {
+  using minijson::Value;
+  auto set_null = [&](const char* k) {
+    auto p = v.get(k);
+    return p && !p->is_null();
+  };
+  for (const char* k : {"final_logit_softcapping", "attn_logit_softcapping"})
+    if (set_null(k))
+      return set_err(5, "config.json: %s is not supported (gemma3 without "
+                        "softcapping only)", k);
+  if (auto p = v.get("hidden_activation"))
+    if (!p->is_null() && p->str != "gelu_pytorch_tanh")
+      return set_err(5, "config.json: hidden_activation %s is not supported "
+                        "(gemma3 runs gelu_pytorch_tanh)", p->str.c_str());
+  if (auto p = v.get("use_bidirectional_attention"))
+    if (p->bool_or(false))
+      return set_err(5, "config.json: use_bidirectional_attention true is "
+                        "not supported");
+  c->tied = true;
+  c->qk_norm = true;
+  c->window = 4096;  // sliding_window, if present, overwrites it below
+  c->qpas = 256.f;
+  if (auto p = v.get("query_pre_attn_scalar"))
+    if (p->kind == Value::Num) c->qpas = (float)p->num;
+  if (!(c->qpas > 0))
+    return set_err(5, "config.json: query_pre_attn_scalar %g must be > 0",
+                   (double)c->qpas);
+  // layer kinds: layer_types in any order, or sliding_window_pattern
+  c->local.assign(c->layers, 0);
+  auto lt = v.get("layer_types");
+  if (lt && lt->kind == Value::Arr) {
+    if ((int)lt->arr.size() != c->layers)
+      return set_err(5, "config.json: layer_types has %d entries for %d "
+                        "layers", (int)lt->arr.size(), c->layers);
+    for (int i = 0; i < c->layers; ++i) {
+      const std::string& s = lt->arr[i]->str;
+      if (s != "sliding_attention" && s != "full_attention")
+        return set_err(5, "config.json: layer_types[%d] %s is not supported",
+                       i, s.c_str());
+      c->local[i] = s == "sliding_attention";
+    }
+  } else {
+    int pat = 6;
+    if (auto p = v.get("sliding_window_pattern"))
+      if (p->kind == Value::Num) pat = (int)p->num;
+    if (pat < 1)
+      return set_err(5, "config.json: sliding_window_pattern %d", pat);
+    for (int i = 0; i < c->layers; ++i) c->local[i] = (i + 1) % pat != 0;
+  }
+  // rope: rope_parameters {full_attention, sliding_attention}, or rope_theta
+  // + rope_local_base_freq + rope_scaling (which concerns the global layers)
+  c->rope_theta = 1e6f;
+  c->rope_local_theta = 1e4f;
+  if (auto p = v.get("rope_theta"))
+    if (p->kind == Value::Num) c->rope_theta = (float)p->num;
+  if (auto p = v.get("rope_local_base_freq"))
+    if (p->kind == Value::Num) c->rope_local_theta = (float)p->num;
+  auto one = [&](const minijson::ValuePtr& o, const char* where, float* theta,
+                 float* lin) -> int {
+    if (!o || o->kind != Value::Obj) return 0;
+    if (auto p = o->get("rope_theta"))
+      if (p->kind == Value::Num) *theta = (float)p->num;
+    auto ty = o->get("rope_type");
+    if (!ty) ty = o->get("type");
+    if (!ty || ty->is_null() || ty->str == "default") return 0;
+    if (ty->str != "linear")
+      return set_err(5, "config.json: %s rope type %s is not supported "
+                        "(gemma3: default or linear)", where, ty->str.c_str());
+    auto f = o->get("factor");
+    if (!f || f->kind != Value::Num || !(f->num > 0))
+      return set_err(5, "config.json: %s linear rope needs a factor > 0",
+                     where);
+    *lin = (float)f->num;
+    return 0;
+  };
+  int r;
+  if ((r = one(v.get("rope_scaling"), "rope_scaling", &c->rope_theta,
+               &c->rope_lin)))
+    return r;
+  if (auto rp = v.get("rope_parameters")) {
+    if ((r = one(rp->get("full_attention"), "rope_parameters.full_attention",
+                 &c->rope_theta, &c->rope_lin)))
+      return r;
+    if ((r = one(rp->get("sliding_attention"),
+                 "rope_parameters.sliding_attention", &c->rope_local_theta,
+                 &c->rope_local_lin)))
+      return r;
+  }
+  return 0;
+}
+
 int parse_config(const char* json, ModelConfig* c) {
   minijson::ValuePtr v;
   try {
@@ -74,18 +168,38 @@ int parse_config(const char* json, ModelConfig* c) {
   }
   if (!v || v->kind != minijson::Value::Obj)
     return set_err(5, "config.json: not an object");
+  // gemma3_text, or gemma3 (the multimodal checkpoint) with the text model
+  // nested under text_config: that object is parsed, every missing field
+  // taking HF's Gemma3TextConfig default.  quantization_config stays at the
+  // top level of either form.
+  const minijson::ValuePtr root = v;
+  bool g3 = false;
+  if (auto p = v->get("model_type")) {
+    g3 = p->str == "gemma3_text" || p->str == "gemma3";
+    if (p->str == "gemma3") {
+      auto tc = v->get("text_config");
+      if (tc && tc->kind == minijson::Value::Obj) {
+        v = tc;
+      } else {
+        v = std::make_shared<minijson::Value>();
+        v->kind = minijson::Value::Obj;
+      }
+    }
+  }
   auto geti = [&](const char* k, int d) {
     auto p = v->get(k);
     return p ? (int)p->num_or(d) : d;
   };
-  c->hidden = geti("hidden_size", 0);
-  c->inter = geti("intermediate_size", 0);
-  c->vocab = geti("vocab_size", 0);
-  c->layers = geti("num_hidden_layers", 0);
-  c->nh = geti("num_attention_heads", 0);
-  c->nkv = geti("num_key_value_heads", c->nh);
-  c->head_dim = geti("head_dim", 0);
-  c->max_pos = geti("max_position_embeddings", 4096);
+  c->gemma3 = g3;
+  c->hidden = geti("hidden_size", g3 ? 2304 : 0);
+  c->inter = geti("intermediate_size", g3 ? 9216 : 0);
+  c->vocab = geti("vocab_size", g3 ? 262208 : 0);
+  c->layers = geti("num_hidden_layers", g3 ? 26 : 0);
+  c->nh = geti("num_attention_heads", g3 ? 8 : 0);
+  c->nkv = geti("num_key_value_heads", g3 ? 4 : c->nh);
+  c->head_dim = geti("head_dim", g3 ? 256 : 0);
+  c->max_pos = geti("max_position_embeddings", g3 ? 131072 : 4096);
+  if (g3) c->rms_eps = 1e-6f;
   if (auto p = v->get("rms_norm_eps")) c->rms_eps = (float)p->num;
   if (auto p = v->get("rope_theta")) c->rope_theta = (float)p->num;
   if (auto p = v->get("tie_word_embeddings")) c->tied = p->bool_or(false);
@@ -98,6 +212,10 @@ int parse_config(const char* json, ModelConfig* c) {
     // (num_key_value_heads already defaults to the head count above)
     c->fused_ckpt = p->str == "phi3";
     if (c->fused_ckpt && !v->get("rope_theta")) c->rope_theta = 1e6f;
+  }
+  if (g3) {
+    int r = parse_gemma3(*v, c);
+    if (r) return r;
   }
   // A bias this engine would silently drop is refused: only qwen2's q/k/v
   // bias is implemented (no o-proj or MLP bias, none under QK-norm).
@@ -119,7 +237,7 @@ int parse_config(const char* json, ModelConfig* c) {
   if (auto p = v->get("max_window_layers"))
     if (p->kind == minijson::Value::Num) c->mwl = (int)p->num;
   if (auto lt = v->get("layer_types"))
-    if (lt->kind == minijson::Value::Arr) {
+    if (lt->kind == minijson::Value::Arr && !g3) {
       // condense to the full-then-sliding boundary; reject other patterns
       int first_sliding = -1;
       for (size_t i = 0; i < lt->arr.size(); ++i) {
@@ -131,10 +249,16 @@ int parse_config(const char* json, ModelConfig* c) {
       }
       c->mwl = first_sliding < 0 ? c->layers : first_sliding;
     }
-  if (auto qc = v->get("quantization_config"))
+  auto qc = v->get("quantization_config");
+  if (!qc) qc = root->get("quantization_config");
+  if (qc)
     if (auto qm = qc->get("quant_method")) {
       c->fp8 = qm->str == "fp8";
       c->w4 = qm->str == "gptq";
+      if (g3 && (c->fp8 || c->w4))
+        return set_err(5, "config.json: quant_method %s with model_type "
+                          "gemma3 is not supported (the fp8 and gptq gate-up "
+                          "kernels have no GELU form)", qm->str.c_str());
       if (c->fp8) {
         // the kernels and the loader's scale offsets are built for 128 x 128
         // blocks (fp8.rs:17); absent (or null) means that default
@@ -293,6 +417,12 @@ static void build_rope_tables(const ModelConfig& c, int max_seq,
   std::vector<float> theta(half);
   for (int i = 0; i < half; ++i)
     theta[i] = 1.0f / powf(c.rope_theta, (float)(2 * i) / (float)rd);
+  // gemma3: either table, with rope type "linear" as inv_freq / factor; in
+  // double and rounded once, like the LongRoPE frequencies below
+  if (c.gemma3)
+    for (int i = 0; i < half; ++i)
+      theta[i] = (float)(1.0 / ((double)c.rope_lin *
+                                pow((double)c.rope_theta, 2.0 * i / (double)rd)));
   // LongRoPE (HF _compute_longrope_parameters): inv_freq_i =
   // 1 / (f_i * theta^(2i/rd)) and both tables times the attention factor m.
   // The list is chosen ONCE, by the engine's max_seq: long_factor if max_seq
@@ -344,9 +474,21 @@ static void build_rope_tables(const ModelConfig& c, int max_seq,
 // The tables engine create builds for this config and max_seq (host only).
 extern "C" int cake_hip_rope_tables(const char* config_json, int max_seq,
                                     float* cosv, float* sinv, int* rd_out) {
+  return cake_hip_rope_tables_ex(config_json, max_seq, 0, cosv, sinv, rd_out);
+}
+// which: 0 = the (global) table every model has, 1 = the local layers' table
+// of a gemma3 config
+extern "C" int cake_hip_rope_tables_ex(const char* config_json, int max_seq,
+                                       int which, float* cosv, float* sinv,
+                                       int* rd_out) {
   ModelConfig c;
   int r = parse_config(config_json, &c);
   if (r) return r;
+  if (which != 0 && which != 1)
+    return set_err(5, "rope_tables: which %d not in {0, 1}", which);
+  if (which == 1 && !c.gemma3)
+    return set_err(5, "rope_tables: only a gemma3 config has a local table");
+  if (which == 1) c = c.local_rope();
   if (max_seq < 32 || max_seq % 32 != 0)
     return set_err(5, "rope_tables: max_seq %d must be a positive multiple of "
                       "32 (engine create rounds up to one)", max_seq);
@@ -355,6 +497,22 @@ extern "C" int cake_hip_rope_tables(const char* config_json, int max_seq,
   if (cosv) memcpy(cosv, ct.data(), ct.size() * sizeof(float));
   if (sinv) memcpy(sinv, st.data(), st.size() * sizeof(float));
   if (rd_out) *rd_out = c.rd();
+  return 0;
+}
+
+// Host only: what engine create plans for one layer of this config.
+extern "C" int cake_hip_layer_dispatch(const char* config_json, int layer,
+                                       int* window, int* rope_table,
+                                       float* q_scale) {
+  ModelConfig c;
+  int r = parse_config(config_json, &c);
+  if (r) return r;
+  if (layer < 0 || layer >= c.layers)
+    return set_err(5, "layer_dispatch: layer %d outside [0,%d)", layer,
+                   c.layers);
+  if (window) *window = c.win_for(layer);
+  if (rope_table) *rope_table = c.gemma3 && c.is_local(layer) ? 1 : 0;
+  if (q_scale) *q_scale = c.gemma3 ? c.q_fold() : 1.f;
   return 0;
 }
 
@@ -456,7 +614,9 @@ static void enqueue_norm_proj(cake_engine* e, const Proj& p, const u16* nw,
                      e->stream);
     return;
   }
-  StatScope ss(e, gateup ? "gemv_gateup" : "gemv_qkv",
+  const bool gelu = gateup && e->c.gemma3;  // bf16 only (parse_config)
+  StatScope ss(e, gelu ? "gemv_gateup_gelu" : gateup ? "gemv_gateup"
+                                                      : "gemv_qkv",
                p.bytes() + 2.0 * K * 2 + out_bytes, flops);
   // x as the GEMV reads it, and the norm weight it applies itself (if any)
   const u16* x = e->x;
@@ -479,6 +639,9 @@ static void enqueue_norm_proj(cake_engine* e, const Proj& p, const u16* nw,
     else
       launch_gemv_fp8(p.fp8(), p.aux, x, out, nullptr, fused_nw, fused_eps,
                       N, K, 0, e->stream, nio);
+  } else if (gelu) {
+    launch_gemv_gateup_gelu(p.bf16(), x, out, fused_nw, fused_eps, I, K,
+                            e->gu_rows, e->stream);
   } else if (gateup) {
     launch_gemv_gateup(p.bf16(), x, out, fused_nw, fused_eps, I, K,
                        e->gu_rows, e->stream);
@@ -515,6 +678,20 @@ static void enqueue_res_proj(cake_engine* e, const Proj& p, const char* fam,
   } else {
     launch_gemv(p.bf16(), a, e->x, e->x, nullptr, 0.f, N, K, 1, e->stream);
   }
+}
+
+// gemma3 decode: t = p . a with no residual (t is e->xn, free once the norm
+// GEMV before it has run), then e->x = bf16(e->x + bf16(rms_norm(t) * post)).
+static void enqueue_post_proj(cake_engine* e, const Proj& p, const char* fam,
+                              const u16* a, const u16* post) {
+  const int N = p.N, K = p.K;
+  {
+    StatScope ss(e, fam, p.bytes() + K * 2 + N * 2, 2.0 * N * K);
+    launch_gemv(p.bf16(), a, e->xn, nullptr, nullptr, 0.f, N, K, 0,
+                e->stream);
+  }
+  StatScope ss(e, "postnorm_add", 4.0 * N * 2, 0);
+  launch_postnorm_add(e->x, e->xn, post, 1, N, e->c.rms_eps, e->stream);
 }
 
 // Prefill: the bf16 (N, K) weight launch_gemm reads.  fp8 and gptq dequantize
@@ -554,7 +731,7 @@ static void enqueue_layer_decode(cake_engine* e, LayerDev& l,
     StatScope ss(e, "gemv_qkv", l.qkv.bytes() + 2.0 * H * 2 + Nq * 2,
                  2.0 * Nq * H);
     launch_gemv_qkv_rope(l.qkv.bf16(), e->x, e->qkv, l.rms1, c.rms_eps, l.kc,
-                         l.vc, l.vtc, e->cos_t, e->sin_t, e->dev_pos, c.nh,
+                         l.vc, l.vtc, l.cos_t, l.sin_t, e->dev_pos, c.nh,
                          c.nkv, hd, c.rd(), e->max_seq, H, e->stream, l.bqkv);
   } else {
     enqueue_norm_proj(e, l.qkv, l.rms1, false,
@@ -562,7 +739,7 @@ static void enqueue_layer_decode(cake_engine* e, LayerDev& l,
     // [Qwen3 QK-norm, attention.rs:202-215 | qwen2 bias, fused +] rope +
     // KV store
     StatScope ss(e, "rope_store", 0, 0);
-    launch_rope_store_decode(e->qkv, l.kc, l.vc, l.vtc, e->cos_t, e->sin_t,
+    launch_rope_store_decode(e->qkv, l.kc, l.vc, l.vtc, l.cos_t, l.sin_t,
                              e->dev_pos, c.nh, c.nkv, hd, c.rd(), e->max_seq,
                              l.qnorm, l.knorm, c.rms_eps, e->stream, l.bqkv);
   }
@@ -573,6 +750,12 @@ static void enqueue_layer_decode(cake_engine* e, LayerDev& l,
     launch_attn_decode(e->qkv, l.kc, l.vc, e->dev_pos, e->attn_ws,
                        e->attn_cnt, e->attn_out, c.nh, c.nkv, hd, e->max_seq,
                        e->nchunk, c.win_for(l.idx), e->stream);
+  }
+  if (c.gemma3) {  // sandwich norms: o and down go through their post-norm
+    enqueue_post_proj(e, l.o, "gemv_o", e->attn_out, l.post1);
+    enqueue_norm_proj(e, l.gu, l.rms2, true, nullptr, e->act);
+    enqueue_post_proj(e, l.down, "gemv_down", e->act, l.post2);
+    return;
   }
   enqueue_res_proj(e, l.o, "gemv_o", e->attn_out, 1);
   // rms_2 -> gate_up GEMV + silu_mul (mlp.rs:21-31)
@@ -599,7 +782,7 @@ static void enqueue_layer_prefill(cake_engine* e, LayerDev& l, int S,
   }
   {  // [fused QK-norm | qkv bias +] rope + KV store for all S positions
     StatScope ss(e, "rope_store_pf", 0, 0);
-    launch_rope_store_prefill(e->qkv, l.kc, l.vc, l.vtc, e->cos_t, e->sin_t,
+    launch_rope_store_prefill(e->qkv, l.kc, l.vc, l.vtc, l.cos_t, l.sin_t,
                               pos0, S, c.nh, c.nkv, hd, c.rd(), e->max_seq,
                               Nq, l.qnorm, l.knorm, c.rms_eps, e->stream,
                               l.bqkv);
@@ -616,7 +799,14 @@ static void enqueue_layer_prefill(cake_engine* e, LayerDev& l, int S,
   {
     StatScope ss(e, "gemm_o", (double)H * Sq * 2 + (double)S * (Sq + H) * 2,
                  2.0 * S * H * Sq);
-    launch_gemm(e->attn_out, wo, x, x, S, H, Sq, 1, e->stream);
+    if (c.gemma3)  // into xn (free after the qkv GEMM), no residual
+      launch_gemm(e->attn_out, wo, e->xn, nullptr, S, H, Sq, 0, e->stream);
+    else
+      launch_gemm(e->attn_out, wo, x, x, S, H, Sq, 1, e->stream);
+  }
+  if (c.gemma3) {
+    StatScope ss(e, "postnorm_add_pf", 4.0 * S * H * 2, 0);
+    launch_postnorm_add(x, e->xn, l.post1, S, H, c.rms_eps, e->stream);
   }
   {
     StatScope ss(e, "rmsnorm_pf", 2.0 * S * H * 2, 0);
@@ -629,7 +819,10 @@ static void enqueue_layer_prefill(cake_engine* e, LayerDev& l, int S,
                  4.0 * S * I * H);
     launch_gemm(e->xn, wgu, e->gu, nullptr, S, 2 * I, H, 0, e->stream);
   }
-  {
+  if (c.gemma3) {
+    StatScope ss(e, "gelu_mul", 3.0 * S * I * 2, 0);
+    launch_gelu_mul_rows(e->gu, e->act, S, I, e->stream);
+  } else {
     StatScope ss(e, "silu_mul", 3.0 * S * I * 2, 0);
     launch_silu_mul_rows(e->gu, e->act, S, I, e->stream);
   }
@@ -637,7 +830,14 @@ static void enqueue_layer_prefill(cake_engine* e, LayerDev& l, int S,
   {
     StatScope ss(e, "gemm_down", (double)H * I * 2 + (double)S * (I + H) * 2,
                  2.0 * S * H * I);
-    launch_gemm(e->act, wdown, x, x, S, H, I, 1, e->stream);
+    if (c.gemma3)
+      launch_gemm(e->act, wdown, e->xn, nullptr, S, H, I, 0, e->stream);
+    else
+      launch_gemm(e->act, wdown, x, x, S, H, I, 1, e->stream);
+  }
+  if (c.gemma3) {
+    StatScope ss(e, "postnorm_add_pf", 4.0 * S * H * 2, 0);
+    launch_postnorm_add(x, e->xn, l.post2, S, H, c.rms_eps, e->stream);
   }
 }
 
@@ -672,20 +872,34 @@ static void enqueue_head_sample(cake_engine* e, int S, int advance_by,
 }
 
 // one full decode step on this rank (graph-capturable when world == 1)
+// the token(s) -> x; gemma3 scales the rows by bf16(sqrt(H))
+static void enqueue_embed_token(cake_engine* e, float* nsc) {
+  if (e->c.gemma3)
+    launch_embed_token_scaled(e->embed, e->dev_tok, e->x, e->c.hidden,
+                              e->stream);
+  else
+    launch_embed_token(e->embed, e->dev_tok, e->x, e->c.hidden, e->stream,
+                       nsc, e->c.rms_eps);
+}
+static void enqueue_embed_rows(cake_engine* e, u16* x, int S) {
+  if (e->c.gemma3)
+    launch_embed_rows_scaled(e->embed, e->ids, x, S, e->c.hidden, e->stream);
+  else
+    launch_embed_rows(e->embed, e->ids, x, S, e->c.hidden, e->stream);
+}
+
 static int enqueue_decode_step(cake_engine* e) {
   const ModelConfig& c = e->c;
   const int H = c.hidden;
   float* nsc = (e->c.fp8 && e->fp8_normchain) ? e->nscale : nullptr;
   if (e->world == 1) {
-    launch_embed_token(e->embed, e->dev_tok, e->x, H, e->stream, nsc,
-                       e->c.rms_eps);
+    enqueue_embed_token(e, nsc);
     for (auto& l : e->L) enqueue_layer_decode(e, l);
     enqueue_head_sample(e, 1, 1);
     return 0;
   }
   if (e->rank == 0) {
-    launch_embed_token(e->embed, e->dev_tok, e->x, H, e->stream, nsc,
-                       e->c.rms_eps);
+    enqueue_embed_token(e, nsc);
     for (auto& l : e->L) enqueue_layer_decode(e, l);
     NCCL_TRY(ncclSend(e->x, H, ncclBfloat16, 1, e->comm, e->stream));
     NCCL_TRY(ncclRecv(e->x, H, ncclBfloat16, e->world - 1, e->comm,
@@ -777,6 +991,10 @@ static int engine_build(const char* config_json, int layer_lo, int layer_hi,
       ALLOC(e->mem, l.knorm, u16, hd);
     }
     if (c.qkv_bias) ALLOC(e->mem, l.bqkv, float, Nq);
+    if (c.gemma3) {
+      ALLOC(e->mem, l.post1, u16, H);
+      ALLOC(e->mem, l.post2, u16, H);
+    }
     // zero the caches: positions >= n are masked (weight 0) but 0*NaN from
     // allocator garbage would still poison the PV MFMA
     for (u16** kv : {&l.kc, &l.vc, &l.vtc}) {
@@ -802,6 +1020,20 @@ static int engine_build(const char* config_json, int layer_lo, int layer_hi,
                       hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(e->sin_t, st.data(), st.size() * 4,
                       hipMemcpyHostToDevice));
+    if (c.gemma3) {  // the local layers' table
+      build_rope_tables(c.local_rope(), max_seq, &ct, &st);
+      ALLOC(e->mem, e->cos_l, float, ct.size());
+      ALLOC(e->mem, e->sin_l, float, st.size());
+      HIP_TRY(hipMemcpy(e->cos_l, ct.data(), ct.size() * 4,
+                        hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(e->sin_l, st.data(), st.size() * 4,
+                        hipMemcpyHostToDevice));
+    }
+    for (auto& l : e->L) {
+      const bool loc = c.gemma3 && c.is_local(l.idx);
+      l.cos_t = loc ? e->cos_l : e->cos_t;
+      l.sin_t = loc ? e->sin_l : e->sin_t;
+    }
   }
   // workspaces
   ALLOC(e->mem, e->x, u16, (size_t)BT * H);
@@ -971,7 +1203,7 @@ extern "C" int cake_hip_prefill(cake_engine* e, const uint32_t* tokens,
         // buffer reuse: chunk ci-2's send (comm_stream) must have read
         // xb before this chunk's embed overwrites it
         if (ci >= 2) HIP_TRY(hipStreamWaitEvent(e->stream, evm, 0));
-        launch_embed_rows(e->embed, e->ids, xb, S, H, e->stream);
+        enqueue_embed_rows(e, xb, S);
         for (auto& l : e->L) enqueue_layer_prefill(e, l, S, pos0, xb);
         HIP_TRY(hipEventRecord(evc, e->stream));
         HIP_TRY(hipStreamWaitEvent(e->comm_stream, evc, 0));
@@ -1009,7 +1241,7 @@ extern "C" int cake_hip_prefill(cake_engine* e, const uint32_t* tokens,
       HIP_TRY(hipMemcpyAsync(e->ids, tokens + done, (size_t)S * 4,
                              hipMemcpyHostToDevice, e->stream));
       auto enqueue_chunk = [&]() -> int {
-        launch_embed_rows(e->embed, e->ids, e->x, S, H, e->stream);
+        enqueue_embed_rows(e, e->x, S);
         for (auto& l : e->L) enqueue_layer_prefill(e, l, S, pos0);
         if (e->world > 1) {
           NCCL_TRY(ncclSend(e->x, (size_t)S * H, ncclBfloat16, 1, e->comm,

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
+#include <cmath>
 #include <map>
 #include <set>
 #include <string>
@@ -40,7 +41,33 @@ struct ModelConfig {
                    // rule; HF layer_types condenses to this for the
                    // full-then-sliding pattern); 0 = all layers windowed
   int win_for(int layer_idx) const {
+    if (gemma3) return is_local(layer_idx) ? window : 0;
     return (window > 0 && layer_idx >= mwl) ? window : 0;
+  }
+  // gemma3 (HF Gemma3ForCausalLM): four (1 + w) norms per layer, GELU-tanh
+  // gate, embedding times sqrt(H), local (sliding) and global layers in any
+  // order, each kind with its own rope table, scores scaled by
+  // query_pre_attn_scalar^-0.5.  `local` holds one flag per layer.
+  bool gemma3 = false;
+  std::vector<char> local;
+  bool is_local(int layer_idx) const {
+    return layer_idx >= 0 && layer_idx < (int)local.size() && local[layer_idx];
+  }
+  // rope of the local layers; rope_theta / rope_lin are the global layers'.
+  // rope_lin: rope type "linear", inv_freq / factor (1 = unscaled)
+  float rope_local_theta = 10000.f, rope_local_lin = 1.f, rope_lin = 1.f;
+  float qpas = 0;  // query_pre_attn_scalar; 0 = head_dim
+  // the factor folded into the q-norm row so that the kernels' hd^-0.5 scores
+  // come out as qpas^-0.5
+  float q_fold() const {
+    return qpas > 0 && qpas != (float)hd() ? sqrtf((float)hd() / qpas) : 1.f;
+  }
+  // this config with the local layers' rope in the global fields
+  ModelConfig local_rope() const {
+    ModelConfig c = *this;
+    c.rope_theta = rope_local_theta;
+    c.rope_lin = rope_local_lin;
+    return c;
   }
   float rms_eps = 1e-5f, rope_theta = 10000.f;
   bool tied = false, qk_norm = false;
@@ -129,6 +156,12 @@ struct LayerDev {
   // (mlp.rs:38-46), down
   Proj qkv, o, gu, down;
   u16 *qnorm = nullptr, *knorm = nullptr;
+  // gemma3: rms2 is pre_feedforward_layernorm; post1 / post2 are
+  // post_attention_layernorm / post_feedforward_layernorm, applied to the o
+  // and down outputs ahead of the residual add; null otherwise
+  u16 *post1 = nullptr, *post2 = nullptr;
+  // this layer's rope tables (gemma3 local layers: the local pair)
+  const float *cos_t = nullptr, *sin_t = nullptr;
   // qwen2: fused q|k|v projection bias, (Nq) f32 in qkv's row order (f32 so
   // that an F16 bias of a GPTQ checkpoint stays exact); null otherwise
   float* bqkv = nullptr;
@@ -175,6 +208,7 @@ struct cake_engine {
   // lm_head aliases embed for a tied model that holds both
   u16 *embed = nullptr, *norm_w = nullptr, *lm_head = nullptr;
   float *cos_t = nullptr, *sin_t = nullptr;
+  float *cos_l = nullptr, *sin_l = nullptr;  // gemma3 local layers' tables
 
   // workspaces
   u16 *x = nullptr, *xn = nullptr, *qkv = nullptr, *attn_out = nullptr;

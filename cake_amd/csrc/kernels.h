@@ -113,6 +113,22 @@ void launch_embed_token(const u16* embed, const u32* tok, u16* x, int H,
                         float eps = 1e-5f);
 void launch_embed_rows(const u16* embed, const u32* ids, u16* x, int S, int H,
                        hipStream_t s);
+// Gemma 3 (kernels_gemma.hip).  Norm rows carry 1 + w folded in.
+// x (rows, cols) = bf16(x + bf16(rms_norm(t) * w)) in place; cols % 8 == 0,
+// cols <= 16384; t must not alias x
+void launch_postnorm_add(u16* x, const u16* t, const u16* w, int rows,
+                         int cols, float eps, hipStream_t s);
+// the GELU-tanh twins of launch_gemv_gateup and launch_silu_mul_rows
+void launch_gemv_gateup_gelu(const u16* W, const u16* x, u16* out,
+                             const u16* nw, float eps, int I, int K, int rows,
+                             hipStream_t s);
+void launch_gelu_mul_rows(const u16* gu, u16* out, int S, int I,
+                          hipStream_t s);
+// embedding gathers times bf16(sqrt(H)), rounded to bf16; H % 8 == 0
+void launch_embed_token_scaled(const u16* embed, const u32* tok, u16* x, int H,
+                               hipStream_t s);
+void launch_embed_rows_scaled(const u16* embed, const u32* ids, u16* x, int S,
+                              int H, hipStream_t s);
 // bias: the fused q|k|v projection bias row ((nh + 2*nkv)*hd f32, qwen2), added
 // to the raw row in f32 before the rotation / the V store; null = none
 void launch_rope_store_decode(u16* qkv, u16* kc, u16* vc, u16* vtc,

@@ -1040,8 +1040,10 @@ extern "C" int cake_hip_decode_dispatch(const char* config_json,
     plain_dispatch(c.nqkv(), H, quant, out);
   }
   plain_dispatch(H, c.sq(), quant, out + 3);
-  out[6] = c.w4 ? CAKE_HIP_FAM_GATEUP_W4
-                : c.fp8 ? CAKE_HIP_FAM_GATEUP_FP8 : CAKE_HIP_FAM_GATEUP;
+  out[6] = c.w4       ? CAKE_HIP_FAM_GATEUP_W4
+           : c.fp8    ? CAKE_HIP_FAM_GATEUP_FP8
+           : c.gemma3 ? CAKE_HIP_FAM_GATEUP_GELU
+                      : CAKE_HIP_FAM_GATEUP;
   out[7] = c.w4 || c.fp8 ? 4 : gemv_gateup_rows_policy();
   out[8] = c.w4 ? gemv_w4_kb(H) : c.fp8 ? gemv_fp8_kb(H) : gemv_kb(H);
   plain_dispatch(H, I, quant, out + 9);
@@ -1293,3 +1295,115 @@ extern "C" int cake_hip_op_embed(int Vt, int H, int S, int mode,
   return ob_down16(b, dout, n + OPG, out);
 }
 
+// ---- gemma3 op entries (kernels_gemma.hip) ---------------------------------
+// x (S, H) = bf16(x + bf16(rms_norm(t) * w)) in place, through the launcher
+// both routes use: S == 1 is the decode launch (one wide block), S > 1 the
+// prefill one.
+extern "C" int cake_hip_op_postnorm_add(int S, int H, float eps,
+                                        const float* x, const float* t,
+                                        const float* w, float* out,
+                                        int device) {
+  const char* who = "op_postnorm_add";
+  if (H < 8 || H > 16384 || H % 8 != 0)
+    return set_err(5, "%s: H %d must be a multiple of 8 in [8,16384]", who, H);
+  if (S < 1 || S > 4096) return set_err(5, "%s: S %d outside [1,4096]", who, S);
+  if (!x || !t || !w || !out) return set_err(5, "%s: null argument", who);
+  OpBufs b;
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreate(&b.s));
+  int r;
+  const size_t n = (size_t)S * H;
+  u16 *dx, *dt, *dw, *dout;
+  if ((r = ob_up16(b, x, n, &dx))) return r;
+  if ((r = ob_up16(b, t, n, &dt))) return r;
+  if ((r = ob_up16(b, w, H, &dw))) return r;
+  if ((r = ob_sent16(b, n + OPG, &dout))) return r;
+  HIP_TRY(hipMemcpyAsync(dout, dx, n * 2, hipMemcpyDeviceToDevice, b.s));
+  launch_postnorm_add(dout, dt, dw, S, H, eps, b.s);
+  HIP_TRY(hipGetLastError());
+  return ob_down16(b, dout, n + OPG, out);
+}
+
+// The bf16 gate-up GEMV with the GELU-tanh gate; arguments as the bf16 form
+// of cake_hip_op_gemv_gateup.
+extern "C" int cake_hip_op_gemv_gateup_gelu(int I, int K, int rows,
+                                            const float* x, const float* w,
+                                            const float* nw, float eps,
+                                            float* out, int device) {
+  const char* who = "op_gemv_gateup_gelu";
+  if (I < 1) return set_err(5, "%s: I %d < 1", who, I);
+  if (K < 8 || K % 8 != 0 || K > 16384)
+    return set_err(5, "%s: K must be a multiple of 8 in [8,16384] (got %d)",
+                   who, K);
+  if (!x || !w || !out) return set_err(5, "%s: x, w and out are required", who);
+  if (rows != 0 && rows != 4 && rows != 8)
+    return set_err(5, "%s: rows %d not in {0,4,8}", who, rows);
+  OpBufs b;
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreate(&b.s));
+  int r;
+  u16 *dx, *dw, *dnw = nullptr, *dout;
+  if ((r = ob_up16(b, x, K, &dx))) return r;
+  if (nw && (r = ob_up16(b, nw, K, &dnw))) return r;
+  if ((r = ob_sent16(b, (size_t)I + OPG, &dout))) return r;
+  if ((r = ob_up16(b, w, (size_t)2 * I * K, &dw))) return r;
+  launch_gemv_gateup_gelu(dw, dx, dout, dnw, eps, I, K, rows, b.s);
+  HIP_TRY(hipGetLastError());
+  return ob_down16(b, dout, (size_t)I + OPG, out);
+}
+
+extern "C" int cake_hip_op_gelu_mul_rows(int S, int I, const float* gu,
+                                         float* out, int device) {
+  const char* who = "op_gelu_mul_rows";
+  if (S < 1 || S > 4096 || I < 1)
+    return set_err(5, "%s: S %d in [1,4096] and I %d >= 1", who, S, I);
+  if (!gu || !out) return set_err(5, "%s: gu and out are required", who);
+  OpBufs b;
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreate(&b.s));
+  int r;
+  u16 *dgu, *dout;
+  if ((r = ob_up16(b, gu, (size_t)S * 2 * I, &dgu))) return r;
+  if ((r = ob_sent16(b, (size_t)S * I + OPG, &dout))) return r;
+  launch_gelu_mul_rows(dgu, dout, S, I, b.s);
+  HIP_TRY(hipGetLastError());
+  return ob_down16(b, dout, (size_t)S * I + OPG, out);
+}
+
+// The scaled embedding gathers; mode 0: launch_embed_rows_scaled on S ids,
+// 1: launch_embed_token_scaled on one id.  Other arguments as
+// cake_hip_op_embed.
+extern "C" int cake_hip_op_embed_scaled(int Vt, int H, int S, int mode,
+                                        const float* table,
+                                        const uint32_t* ids, float* out,
+                                        int device) {
+  const char* who = "op_embed_scaled";
+  if (mode < 0 || mode > 1) return set_err(5, "%s: mode %d", who, mode);
+  if (H < 8 || H > 16384 || H % 8 != 0)
+    return set_err(5, "%s: H %d must be a multiple of 8 in [8,16384]", who, H);
+  if (Vt < 1 || Vt > (1 << 20))
+    return set_err(5, "%s: Vt %d outside [1,%d]", who, Vt, 1 << 20);
+  if (S < 1 || S > 4096 || (mode != 0 && S != 1))
+    return set_err(5, "%s: S %d (rows: 1..4096, token: 1)", who, S);
+  if (!table || !ids || !out) return set_err(5, "%s: null argument", who);
+  for (int i = 0; i < S; ++i)
+    if (ids[i] >= (uint32_t)Vt)
+      return set_err(5, "%s: id %u outside the table (%d rows)", who, ids[i],
+                     Vt);
+  OpBufs b;
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreate(&b.s));
+  int r;
+  const size_t n = (size_t)S * H;
+  u16 *dt, *dout;
+  void* dids;
+  if ((r = ob_up16(b, table, (size_t)Vt * H, &dt))) return r;
+  if ((r = ob_upf32(b, ids, (size_t)S * 4, &dids))) return r;
+  if ((r = ob_sent16(b, n + OPG, &dout))) return r;
+  if (mode == 0)
+    launch_embed_rows_scaled(dt, (const u32*)dids, dout, S, H, b.s);
+  else
+    launch_embed_token_scaled(dt, (const u32*)dids, dout, H, b.s);
+  HIP_TRY(hipGetLastError());
+  return ob_down16(b, dout, n + OPG, out);
+}

@@ -144,6 +144,30 @@ static int upload_weight(cake_engine* e, u16* dst, const char* filebase,
   return 0;
 }
 
+// A gemma3 norm row: bf16((1 + w) * mul), the sum and the product in f32 and
+// one rounding (HF's Gemma3RMSNorm multiplies by 1 + w.float(); folding it
+// here leaves every norm kernel its plain bf16 weight row).  mul is 1, or for
+// q_norm the score-scale fold sqrt(head_dim / query_pre_attn_scalar).
+static int upload_norm_1pw(cake_engine* e, u16* dst, const char* filebase,
+                           const StTensor& t, size_t expect, float mul) {
+  if (t.elems() != expect)
+    return set_err(5, "tensor shape mismatch: got %zu want %zu elems",
+                   t.elems(), expect);
+  std::vector<float> w;
+  if (!st_to_f32(t, filebase, expect, &w))
+    return set_err(5, "unsupported safetensors dtype %s", t.dtype.c_str());
+  std::vector<u16> tmp(expect);
+  for (size_t i = 0; i < expect; ++i) {
+    union { float f; unsigned u; } v{(1.0f + w[i]) * mul};
+    unsigned r = ((v.u & 0x7fffffffu) > 0x7f800000u)
+                     ? 0x7fc00000u
+                     : v.u + 0x7fffu + ((v.u >> 16) & 1u);
+    tmp[i] = (u16)(r >> 16);
+  }
+  HIP_TRY(hipMemcpy(dst, tmp.data(), expect * 2, hipMemcpyHostToDevice));
+  return 0;
+}
+
 // one projection's bias vector -> f32 (every source dtype widens exactly)
 static int upload_bias(cake_engine* e, float* dst, const char* filebase,
                        const StTensor& t, const std::string& name,
@@ -354,13 +378,40 @@ static int load_safetensors_file(cake_engine* e, const char* path) {
                       hipMemcpyHostToDevice));
     return 0;
   };
+  // The text model's tensor prefix.  A gemma3 checkpoint saved from the
+  // multimodal class nests it (and carries vision tensors, which nothing
+  // here asks for): the first candidate any tensor of this file starts with.
+  std::string mp = "model.";
+  if (c.gemma3)
+    for (const char* cand : {"model.language_model.", "language_model.model.",
+                             "model."}) {
+      const std::string cs(cand);
+      bool hit = false;
+      for (auto& kv : tensors)
+        if (kv.first.compare(0, cs.size(), cs) == 0 &&
+            (kv.first.compare(cs.size(), 7, "layers.") == 0 ||
+             kv.first.compare(cs.size(), 13, "embed_tokens.") == 0 ||
+             kv.first.compare(cs.size(), 5, "norm.") == 0)) {
+          hit = true;
+          break;
+        }
+      if (hit) {
+        mp = cs;
+        break;
+      }
+    }
+  // a plain norm row, or gemma3's (1 + w) form
+  auto upload_norm = [&](u16* dst, size_t n, float mul) -> int {
+    return c.gemma3 ? upload_norm_1pw(e, dst, base, t, n, mul)
+                    : upload_weight(e, dst, base, t, n);
+  };
   if (e->has_embed()) {
-    LOADW("model.embed_tokens.weight", upload_weight(e, e->embed, base, t, V * H));
+    LOADW(mp + "embed_tokens.weight", upload_weight(e, e->embed, base, t, V * H));
   }
   if (e->has_head()) {
-    LOADW("model.norm.weight", upload_weight(e, e->norm_w, base, t, H));
+    LOADW(mp + "norm.weight", upload_norm(e->norm_w, H, 1.f));
     if (!(c.tied && e->has_embed())) {
-      std::string name = c.tied ? "model.embed_tokens.weight"
+      std::string name = c.tied ? mp + "embed_tokens.weight"
                                 : "lm_head.weight";
       LOADW(name, upload_weight(e, e->lm_head, base, t, V * H));
     }
@@ -391,10 +442,16 @@ static int load_safetensors_file(cake_engine* e, const char* path) {
   for (int li = e->lo; li < e->hi; ++li) {
     LayerDev& l = e->L[li - e->lo];
     char p[128];
-    snprintf(p, sizeof p, "model.layers.%d.", li);
-    std::string pre(p);
-    LOADW(pre + "input_layernorm.weight", upload_weight(e, l.rms1, base, t, H));
-    LOADW(pre + "post_attention_layernorm.weight", upload_weight(e, l.rms2, base, t, H));
+    snprintf(p, sizeof p, "layers.%d.", li);
+    std::string pre = mp + p;
+    LOADW(pre + "input_layernorm.weight", upload_norm(l.rms1, H, 1.f));
+    if (c.gemma3) {  // rms2 is the norm ahead of the MLP in every family
+      LOADW(pre + "post_attention_layernorm.weight", upload_norm(l.post1, H, 1.f));
+      LOADW(pre + "pre_feedforward_layernorm.weight", upload_norm(l.rms2, H, 1.f));
+      LOADW(pre + "post_feedforward_layernorm.weight", upload_norm(l.post2, H, 1.f));
+    } else {
+      LOADW(pre + "post_attention_layernorm.weight", upload_weight(e, l.rms2, base, t, H));
+    }
     const Proj* projs[4] = {&l.qkv, &l.o, &l.gu, &l.down};
     for (int pi = 0; pi < 4; ++pi) {
       const Proj& pj = *projs[pi];
@@ -433,8 +490,8 @@ static int load_safetensors_file(cake_engine* e, const char* path) {
       }
     }
     if (c.qk_norm) {
-      LOADW(pre + "self_attn.q_norm.weight", upload_weight(e, l.qnorm, base, t, hd));
-      LOADW(pre + "self_attn.k_norm.weight", upload_weight(e, l.knorm, base, t, hd));
+      LOADW(pre + "self_attn.q_norm.weight", upload_norm(l.qnorm, hd, c.q_fold()));
+      LOADW(pre + "self_attn.k_norm.weight", upload_norm(l.knorm, hd, 1.f));
     }
   }
 #undef LOADW
@@ -495,8 +552,13 @@ extern "C" int cake_hip_init_random(cake_engine* e, uint64_t seed,
     const Proj* projs[4] = {&l.qkv, &l.o, &l.gu, &l.down};
     for (int i = 0; i < 4; ++i) fill_proj(*projs[i], salted(base + i));
     if (l.qnorm) {
-      launch_fill_const(l.qnorm, hd, 1.0f, e->stream);
+      // gemma3: w = 0, so 1 + w = 1, times the score-scale fold on q
+      launch_fill_const(l.qnorm, hd, c.gemma3 ? c.q_fold() : 1.0f, e->stream);
       launch_fill_const(l.knorm, hd, 1.0f, e->stream);
+    }
+    if (l.post1) {
+      launch_fill_const(l.post1, H, 1.0f, e->stream);
+      launch_fill_const(l.post2, H, 1.0f, e->stream);
     }
     if (l.bqkv) {
       // slot 4 of the layer: q and k rows ~uniform(+-3) (real qwen2 q/k

@@ -286,8 +286,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="llama3-8b",
                     help="a name from configs.MODELS, QUANT_MODELS, "
-                    "QWEN2_MODELS, PHI_MODELS or FALCON3_MODELS (e.g. "
-                    "phi-4-mini, falcon3-7b)")
+                    "QWEN2_MODELS, PHI_MODELS, FALCON3_MODELS or "
+                    "GEMMA3_MODELS (e.g. phi-4-mini, falcon3-7b, "
+                    "gemma-3-4b)")
     ap.add_argument("--safetensors", default=None)
     ap.add_argument("--tokenizer", default=None,
                     help="path to a tokenizer.json")

@@ -401,6 +401,7 @@ enum {
   CAKE_HIP_FAM_GEMM = 8,
   CAKE_HIP_FAM_GEMV_W4 = 9,
   CAKE_HIP_FAM_GATEUP_W4 = 10,
+  CAKE_HIP_FAM_GATEUP_GELU = 11, /* gemma3: the GELU-tanh twin of GATEUP */
 };
 /* fp8 is the quant selector: 0 bf16, 1 fp8.  The 4-bit (gptq) kernels need a
  * group size and are queried through cake_hip_linear_dispatch_w4. */
@@ -424,6 +425,18 @@ int cake_hip_decode_dispatch(const char *config_json, int out[15]);
  * the rotary fields is reported here as well (error 5). */
 int cake_hip_rope_tables(const char *config_json, int max_seq, float *cosv,
                          float *sinv, int *rd_out);
+/* cake_hip_rope_tables with a table selector: which 0 is that table (the
+ * global layers' of a gemma3 config), which 1 the local (sliding) layers'
+ * table, which only a gemma3 config has (error 5 otherwise). */
+int cake_hip_rope_tables_ex(const char *config_json, int max_seq, int which,
+                            float *cosv, float *sinv, int *rd_out);
+/* Host only: what engine create plans for layer `layer` of config_json:
+ * *window the attention span (0 = full), *rope_table 0 (global) or 1 (the
+ * gemma3 local table), *q_scale the factor folded into the q-norm row
+ * (sqrt(head_dim / query_pre_attn_scalar) for gemma3, else 1).  Any of the
+ * three may be NULL.  Every config refusal of create is reported (error 5). */
+int cake_hip_layer_dispatch(const char *config_json, int layer, int *window,
+                            int *rope_table, float *q_scale);
 
 /* ---- observability (bench roofline evidence) ----------------------------
  * JSON {"kernels": {name: {"launches": n, "ms": t, "bytes": b}}} — per-
@@ -501,6 +514,32 @@ int cake_hip_op_argmax(int V, const float *logits, float temperature,
 int cake_hip_op_embed(int Vt, int H, int S, int mode, const float *table,
                       const uint32_t *ids, float eps, float *out,
                       float *nscale_out, int device);
+/* Test-only, gemma3 (kernels_gemma.hip); outputs carry CAKE_HIP_OP_GUARD
+ * guard elements like the entries above, and arguments are validated before
+ * any device call (error 5).
+ * x (S, H) = bf16(x + bf16(rms_norm(t) * w)), the post-norm + residual add;
+ * S == 1 is the decode launch, S > 1 the prefill one.  H % 8 == 0,
+ * 8 <= H <= 16384, S <= 4096.  out is (S*H + guard). */
+int cake_hip_op_postnorm_add(int S, int H, float eps, const float *x,
+                             const float *t, const float *w, float *out,
+                             int device);
+/* [rms_norm ->] gate-up GEMV -> gelu_pytorch_tanh(gate) * up on bf16 weights
+ * w (2I, K); nw may be NULL (x already normalized).  K % 8 == 0,
+ * 8 <= K <= 16384, rows 0 | 4 | 8.  out is (I + guard). */
+int cake_hip_op_gemv_gateup_gelu(int I, int K, int rows, const float *x,
+                                 const float *w, const float *nw, float eps,
+                                 float *out, int device);
+/* Prefill gelu_mul over S rows of gu (S, 2I) = [gate | up]; any I >= 1 (a
+ * multiple of 8 runs the vector loop the engine uses).  out is
+ * (S*I + guard). */
+int cake_hip_op_gelu_mul_rows(int S, int I, const float *gu, float *out,
+                              int device);
+/* The embedding gathers times bf16(sqrt(H)), rounded to bf16.  mode 0: rows
+ * on S ids; 1: the token form on one id.  Limits as cake_hip_op_embed.  out
+ * is (S*H + guard). */
+int cake_hip_op_embed_scaled(int Vt, int H, int S, int mode,
+                             const float *table, const uint32_t *ids,
+                             float *out, int device);
 int cake_hip_stats_reset(cake_engine *e);
 int cake_hip_set_stats(cake_engine *e, int enabled);
 

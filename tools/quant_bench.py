@@ -28,7 +28,8 @@ SEED = 299792458
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("model", help="a name from MODELS, QUANT_MODELS, "
-                    "QWEN2_MODELS, PHI_MODELS or FALCON3_MODELS")
+                    "QWEN2_MODELS, PHI_MODELS, FALCON3_MODELS or "
+                    "GEMMA3_MODELS")
     ap.add_argument("--steps", type=int, default=256)
     ap.add_argument("--prompt-len", type=int, default=128)
     ap.add_argument("--max-seq", type=int, default=4096)
