@@ -291,7 +291,8 @@ def op_attn_prefill(q, kc, vc, vtc, pos0, window=0, variant=None, device=0):
     cache images kc/vc (nkv, max_seq, hd), vtc (nkv, hd, max_seq).  variant =
     (pfv, nw, split, deep); default: plain v2 NW=8 at hd 128, the MFMA-256
     kernel (1, 4, 0, 0) at hd 256 (its plain kernel is (0, 0, 0, 0)), else the
-    generic kernel.  Returns (S, nh*hd)."""
+    generic kernel (0, 0, 0, 0); hd 64 and 96 also take (1, 4, 0, 0), the MFMA
+    kernel the engine runs there.  Returns (S, nh*hd)."""
     q = np.ascontiguousarray(q, dtype=np.float32)
     S, nh, hd = q.shape
     kc = np.ascontiguousarray(kc, dtype=np.float32)

@@ -154,6 +154,28 @@ GEMMA3_27B = dict(_GEMMA3, hidden_size=5376, intermediate_size=21504,
                   num_key_value_heads=16, head_dim=128,
                   query_pre_attn_scalar=168)
 
+# Small-head models whose prefill attention runs k_attn_prefill_mfma_n:
+# Llama-3.2-1B (head_dim 64, tied head, llama3 rope scaling with factor 32)
+# and Phi-3-mini-4k (HF model_type "phi3", head_dim 96, MHA, fused checkpoint
+# tensors, plain rope).  Shapes from memory, like Falcon3's: a real run reads
+# the checkpoint's config.json.
+LLAMA3_2_1B = dict(
+    model_type="llama", hidden_size=2048, intermediate_size=8192,
+    vocab_size=128256, num_hidden_layers=16, num_attention_heads=32,
+    num_key_value_heads=8, head_dim=64, rms_norm_eps=1e-5,
+    rope_theta=500000.0, max_position_embeddings=131072,
+    tie_word_embeddings=True,
+    rope_scaling=dict(rope_type="llama3", factor=32.0, low_freq_factor=1.0,
+                      high_freq_factor=4.0,
+                      original_max_position_embeddings=8192))
+
+PHI_3_MINI_4K = dict(
+    model_type="phi3", hidden_size=3072, intermediate_size=8192,
+    vocab_size=32064, num_hidden_layers=32, num_attention_heads=32,
+    num_key_value_heads=32, head_dim=96, rms_norm_eps=1e-5,
+    rope_theta=10000.0, max_position_embeddings=4096,
+    tie_word_embeddings=False)
+
 MODELS = {
     "llama3-8b": LLAMA3_8B,
     "llama3-70b": LLAMA3_70B,
@@ -205,11 +227,18 @@ GEMMA3_MODELS = {
 }
 
 
+# head_dim 64 and 96 (MFMA prefill attention k_attn_prefill_mfma_n)
+SMALL_HEAD_MODELS = {
+    "llama3.2-1b": LLAMA3_2_1B,
+    "phi-3-mini-4k": PHI_3_MINI_4K,
+}
+
+
 def find_model(name: str) -> dict:
     """The config called `name` in MODELS, QUANT_MODELS, QWEN2_MODELS,
-    PHI_MODELS, FALCON3_MODELS or GEMMA3_MODELS."""
+    PHI_MODELS, FALCON3_MODELS, GEMMA3_MODELS or SMALL_HEAD_MODELS."""
     for table in (MODELS, QUANT_MODELS, QWEN2_MODELS, PHI_MODELS,
-                  FALCON3_MODELS, GEMMA3_MODELS):
+                  FALCON3_MODELS, GEMMA3_MODELS, SMALL_HEAD_MODELS):
         if name in table:
             return table[name]
     raise KeyError(name)

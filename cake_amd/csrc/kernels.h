@@ -170,6 +170,11 @@ void launch_attn_prefill_256(const u16* qkv, const u16* kc, const u16* vc,
                              int nh, int nkv, int max_seq, int qkv_stride,
                              int out_stride, int window, int mfma,
                              hipStream_t s);
+// hd 64 | 96: k_attn_prefill_mfma_n<hd> (kernels_attn_n.hip; reads kc and vtc)
+void launch_attn_prefill_n(const u16* qkv, const u16* kc, const u16* vtc,
+                           u16* out, int S, int pos0, int nh, int nkv, int hd,
+                           int max_seq, int qkv_stride, int out_stride,
+                           int window, hipStream_t s);
 // ws: split-KV partial workspace (nh * S * 2 * 132 f32) or nullptr to
 // force the single-pass path
 void launch_attn_prefill(const u16* qkv, const u16* kc, const u16* vc,
@@ -180,8 +185,9 @@ void launch_attn_prefill(const u16* qkv, const u16* kc, const u16* vc,
 // >= 2 = LDS-staged kernel with nw (4|8) waves per block, optional split-KV
 // (+ combine pass, only when ws != nullptr and S >= split_min_s) or a deep
 // schedule (1|2, ignored under split).  hd 256: {pfv 1, nw 4} = the MFMA-256
-// kernel, {pfv 0, nw 0} = the plain hd-256 kernel.  Other head dims always
-// run the generic kernel.
+// kernel, {pfv 0, nw 0} = the plain hd-256 kernel.  hd 64 | 96: {pfv 1, nw 4}
+// = k_attn_prefill_mfma_n, {pfv 0, nw 0} = the generic kernel.  Other head
+// dims always run the generic kernel.
 struct PfVariant {
   int pfv = 2, nw = 8, split = 0, deep = 0, split_min_s = 1024;
 };

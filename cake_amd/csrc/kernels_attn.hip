@@ -1794,7 +1794,11 @@ PfVariant attn_prefill_policy(int S, int nh, int hd) {
       getenv("CAKE_PF_SPLIT") ? atoi(getenv("CAKE_PF_SPLIT")) : 0;
   static const int deep_env =
       getenv("CAKE_PF_DEEP") ? atoi(getenv("CAKE_PF_DEEP")) : 0;
-  if (hd == 256) {  // MFMA-256 (v1 structure, 4 waves) or the plain kernel
+  // hd 256: MFMA-256 (v1 structure, 4 waves) or the plain kernel; hd 64 | 96:
+  // k_attn_prefill_mfma_n (4 waves) or the generic kernel.  No size rule at
+  // 64 | 96: the MFMA kernel measured faster than the generic one from
+  // S = 128 up
+  if (hd == 256 || hd == 64 || hd == 96) {
     PfVariant v256;
     v256.pfv = pfv == 0 ? 0 : 1;
     v256.nw = pfv == 0 ? 0 : 4;
@@ -1833,6 +1837,11 @@ void launch_attn_prefill_variant(const u16* qkv, const u16* kc,
   if (hd == 256) {
     launch_attn_prefill_256(qkv, kc, vc, vtc, out, S, pos0, nh, nkv, max_seq,
                             qkv_stride, out_stride, window, pfv != 0, s);
+    return;
+  }
+  if ((hd == 64 || hd == 96) && pfv != 0) {
+    launch_attn_prefill_n(qkv, kc, vtc, out, S, pos0, nh, nkv, hd, max_seq,
+                          qkv_stride, out_stride, window, s);
     return;
   }
   if (hd == 128 && pfv >= 2) {

@@ -288,9 +288,11 @@ extern "C" int cake_hip_op_attn_prefill(int S, int pos0, int nh, int nkv,
   if (window < 0) return set_err(5, "%s: window %d < 0", who, window);
   // what the dispatcher can express: hd 128 -> v1, or v2 with 4|8 waves and
   // at most one of split / deep; hd 256 -> the MFMA-256 kernel {1, 4} or the
-  // plain one {0, 0}; any other hd -> the generic kernel only
+  // plain one {0, 0}; hd 64 | 96 -> k_attn_prefill_mfma_n {1, 4} or the
+  // generic kernel {0, 0}; any other hd -> the generic kernel only
   const bool ok =
-      hd == 256 ? (!split && !deep &&
+      (hd == 256 || hd == 64 || hd == 96)
+                ? (!split && !deep &&
                    ((pfv == 1 && nw == 4) || (pfv == 0 && nw == 0))) :
       hd == 128 ? ((pfv == 1 && nw == 8 && !split && !deep) ||
                    (pfv == 2 && (nw == 4 || nw == 8) &&

@@ -286,9 +286,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="llama3-8b",
                     help="a name from configs.MODELS, QUANT_MODELS, "
-                    "QWEN2_MODELS, PHI_MODELS, FALCON3_MODELS or "
-                    "GEMMA3_MODELS (e.g. phi-4-mini, falcon3-7b, "
-                    "gemma-3-4b)")
+                    "QWEN2_MODELS, PHI_MODELS, FALCON3_MODELS, "
+                    "GEMMA3_MODELS or SMALL_HEAD_MODELS (e.g. phi-4-mini, "
+                    "falcon3-7b, gemma-3-4b, llama3.2-1b)")
     ap.add_argument("--safetensors", default=None)
     ap.add_argument("--tokenizer", default=None,
                     help="path to a tokenizer.json")

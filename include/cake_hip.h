@@ -228,8 +228,9 @@ int cake_hip_op_kv_store_pr(int S, int pos0, int decode, int nh, int nkv,
  * positions pos0.. over the cache images; out (S, nh*hd).  Variant: hd 128
  * takes pfv 1 (nw 8, no split/deep) or pfv 2 with nw 4|8 and at most one of
  * split (0|1) / deep (0|1|2); hd 256 takes {1,4,0,0} (the MFMA-256 kernel)
- * or {0,0,0,0} (the plain hd-256 kernel); any other hd takes {0,0,0,0}
- * (generic kernel). */
+ * or {0,0,0,0} (the plain hd-256 kernel); hd 64 and 96 take {1,4,0,0} (the
+ * MFMA kernel k_attn_prefill_mfma_n, what the engine runs) or {0,0,0,0} (the
+ * generic kernel); any other hd takes {0,0,0,0} (generic kernel). */
 int cake_hip_op_attn_prefill(int S, int pos0, int nh, int nkv, int hd,
                              int max_seq, int window, int pfv, int nw,
                              int split, int deep, const float *q,

@@ -7,7 +7,8 @@ the first token (it comes from the prefill), two warm runs and three timed
 runs of --steps decode steps each.  Prints ONE JSON line; with --stats also
 the eager per-kernel kernel_stats() table (us per launch, achieved GB/s over
 the algorithmic bytes); with --prefill-len N the prefill rate of an N-token
-prompt (two warm passes, one timed).
+prompt (two warm passes, one timed), and under --stats the prefill kernels of
+three eager N-token passes in the same table.
 
   python tools/quant_bench.py llama3-8b
   python tools/quant_bench.py llama3-8b-gptq --stats --prefill-len 2048
@@ -28,8 +29,8 @@ SEED = 299792458
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("model", help="a name from MODELS, QUANT_MODELS, "
-                    "QWEN2_MODELS, PHI_MODELS, FALCON3_MODELS or "
-                    "GEMMA3_MODELS")
+                    "QWEN2_MODELS, PHI_MODELS, FALCON3_MODELS, "
+                    "GEMMA3_MODELS or SMALL_HEAD_MODELS")
     ap.add_argument("--steps", type=int, default=256)
     ap.add_argument("--prompt-len", type=int, default=128)
     ap.add_argument("--max-seq", type=int, default=4096)
@@ -97,6 +98,16 @@ def main():
                 e2.set_stats(True)
                 e2.decode(args.stats_steps)
                 e2.sync()
+                if args.prefill_len > 0:
+                    e2.set_stats(False)
+                    e2.reset()
+                    e2.prefill(pf)             # warm: GEMM plans
+                    e2.sync()
+                    e2.set_stats(True)
+                    for _ in range(3):
+                        e2.reset()
+                        e2.prefill(pf)
+                    e2.sync()
                 e2.set_stats(False)
                 table = e2.kernel_stats()["kernels"]
             finally:
