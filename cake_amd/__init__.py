@@ -103,6 +103,9 @@ def _load_lib():
     lib.cake_hip_op_dequant_w4.argtypes = [c] * 3 + [i32p, i32p, fp, fp, c]
     lib.cake_hip_linear_dispatch_w4.argtypes = [c, c, c, c,
                                                 ctypes.POINTER(c)]
+    lib.cake_hip_op_gemv_mx4.argtypes = [c] * 6 + [fp, u8p, u8p, fp, fp, c]
+    lib.cake_hip_op_gemv_gateup_mx4.argtypes = [c] * 3 + [fp, u8p, u8p, fp, c]
+    lib.cake_hip_op_dequant_mx4.argtypes = [c, c, u8p, u8p, fp, c]
     lib.cake_hip_kernel_stats.argtypes = [p, ctypes.c_char_p, c]
     lib.cake_hip_stats_reset.argtypes = [p]
     lib.cake_hip_set_stats.argtypes = [p, c]
@@ -766,6 +769,64 @@ def linear_dispatch_w4(kind, n, K, group=128):
     return dict(family=LINEAR_FAMILIES[o[0]], rows=o[1], kb=o[2])
 
 
+# ---- MXFP4 op entries (checkpoint layout = device layout) ------------------
+# families past GEMMA3_FAMILIES (CAKE_HIP_FAM_GEMV_MX4 = 12, GATEUP_MX4 = 13)
+MX4_FAMILIES = ("gemv_mx4", "gateup_mx4")
+MX4_DOT2 = {None: -1, "f32": 0, "dot2": 1}   # inner loop; None = the policy
+
+
+def _mx4_tensors(weight, weight_scale):
+    """(N, K, pointers) of one MXFP4 projection: weight (N, K/2) uint8 (low
+    nibble first), weight_scale (N, K/32) uint8 E8M0."""
+    weight = np.asarray(weight)
+    N, K = weight.shape[0], weight.shape[1] * 2
+    return (N, K, _u8(weight, (N, K // 2), "weight"),
+            _u8(weight_scale, (N, K // 32), "weight_scale"))
+
+
+def op_gemv_mx4(x, weight, weight_scale, epi=0, res=None, alias=False,
+                variant=None, device=0):
+    """The MXFP4 GEMV on x (repeats, K) [and res (repeats, N)], one launch per
+    row back to back; variant None | "f32" | "dot2" picks the inner loop.
+    Returns (out (repeats, N), guards (repeats, OP_GUARD))."""
+    N, K, w, sc = _mx4_tensors(weight, weight_scale)
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    x = x[None] if x.ndim == 1 else x
+    repeats = x.shape[0]
+    _, xp = _f32_shaped(x, (repeats, K), "x")
+    _r, rp = _opt_f32(res, (repeats, N), "res")
+    out = np.empty((repeats, N + OP_GUARD), dtype=np.float32)
+    _check(_lib.cake_hip_op_gemv_mx4(
+        N, K, epi, MX4_DOT2[variant], 1 if alias else 0, repeats, xp, w[1],
+        sc[1], rp, out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+        device))
+    return out[:, :N], out[:, N:]
+
+
+def op_gemv_gateup_mx4(x, weight, weight_scale, variant=None, device=0):
+    """The MXFP4 gate-up GEMV -> silu_mul on normalized x (K,); the tensors
+    hold 2I rows, gate then up.  Returns (out (I,), guards)."""
+    N, K, w, sc = _mx4_tensors(weight, weight_scale)
+    I = N // 2
+    _, xp = _f32_shaped(np.ascontiguousarray(x, dtype=np.float32), (K,), "x")
+    out = np.empty(I + OP_GUARD, dtype=np.float32)
+    _check(_lib.cake_hip_op_gemv_gateup_mx4(
+        I, K, MX4_DOT2[variant], xp, w[1], sc[1],
+        out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), device))
+    return out[:I], out[I:]
+
+
+def op_dequant_mx4(weight, weight_scale, device=0):
+    """MXFP4 -> bf16 dequant of one projection.  Returns (out (N, K),
+    guards)."""
+    N, K, w, sc = _mx4_tensors(weight, weight_scale)
+    out = np.empty(N * K + OP_GUARD, dtype=np.float32)
+    _check(_lib.cake_hip_op_dequant_mx4(
+        N, K, w[1], sc[1],
+        out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), device))
+    return out[:N * K].reshape(N, K), out[N * K:]
+
+
 def decode_dispatch(config):
     """The five linear launches of one decode step of a model (host only), by
     the engine's own predicates: {layer: (family, rows, kb)} for qkv, o,
@@ -774,7 +835,7 @@ def decode_dispatch(config):
         config = json.dumps(config)
     o = (ctypes.c_int * 15)()
     _check(_lib.cake_hip_decode_dispatch(config.encode(), o))
-    fams = LINEAR_FAMILIES + GEMMA3_FAMILIES
+    fams = LINEAR_FAMILIES + GEMMA3_FAMILIES + MX4_FAMILIES
     return {k: (fams[o[3 * i]], o[3 * i + 1], o[3 * i + 2])
             for i, k in enumerate(("qkv", "o", "gateup", "down", "head"))}
 

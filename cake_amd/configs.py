@@ -56,6 +56,19 @@ LLAMA3_8B_GPTQ = dict(LLAMA3_8B,
     quantization_config=dict(quant_method="gptq", bits=4, group_size=128,
                              desc_act=False, sym=True))
 
+# AMD Quark MXFP4 (OCP microscaling FP4: e2m1 elements, one e8m0 scale per 32
+# along in_features), the seven projections of every layer; embedding, lm_head
+# and norms 16-bit.  The engine runs it weight-only (bf16 activations).
+QUARK_MXFP4 = dict(
+    quant_method="quark",
+    global_quant_config=dict(weight=dict(
+        dtype="fp4", qscheme="per_group", group_size=32, ch_axis=-1,
+        scale_format="e8m0")),
+    layer_quant_config={}, layer_type_quant_config={}, exclude=["lm_head"])
+LLAMA3_8B_MXFP4 = dict(LLAMA3_8B, quantization_config=QUARK_MXFP4)
+LLAMA3_70B_MXFP4 = dict(LLAMA3_70B, quantization_config=QUARK_MXFP4)
+QWEN3_32B_MXFP4 = dict(QWEN3_32B, quantization_config=QUARK_MXFP4)
+
 # Qwen2.5 (qwen2/): the llama-shaped Transformer plus an additive bias on the
 # q, k and v projections (qwen2/config.rs:84).  The official GPTQ-Int4
 # checkpoints are group 128 without act-order and keep F16 biases.
@@ -189,6 +202,9 @@ MODELS = {
 # quantized variants live beside MODELS (the pinned bf16/fp8 table)
 QUANT_MODELS = {
     "llama3-8b-gptq": LLAMA3_8B_GPTQ,
+    "llama3-8b-mxfp4": LLAMA3_8B_MXFP4,
+    "llama3-70b-mxfp4": LLAMA3_70B_MXFP4,
+    "qwen3-32b-mxfp4": QWEN3_32B_MXFP4,
 }
 
 
@@ -259,11 +275,13 @@ def weight_bytes(cfg: dict, lo=0, hi=None, embed=True, head=True) -> int:
     L = (hi if hi is not None else cfg["num_hidden_layers"]) - lo
     bias = L * (nh + 2 * nkv) * hd * 4 if cfg.get("model_type") == "qwen2" \
         else 0
-    if q.get("quant_method") != "gptq":
+    if q.get("quant_method") not in ("gptq", "quark"):
         return weight_bytes_bf16(cfg, lo, hi, embed, head) + bias
     g = q.get("group_size", 128)
 
     def w4(n, k):
+        if q["quant_method"] == "quark":     # nibbles + one e8m0 byte per 32
+            return n * k // 2 + n * (k // 32)
         return n * k // 2 + n * (k // (k if g == -1 else g)) * 8
     per_layer = (w4((nh + 2 * nkv) * hd, H) + w4(H, nh * hd) +
                  w4(2 * I, H) + w4(H, I) + 2 * H * 2)

@@ -255,7 +255,8 @@ int parse_config(const char* json, ModelConfig* c) {
     if (auto qm = qc->get("quant_method")) {
       c->fp8 = qm->str == "fp8";
       c->w4 = qm->str == "gptq";
-      if (g3 && (c->fp8 || c->w4))
+      c->mx4 = qm->str == "quark";
+      if (g3 && (c->fp8 || c->w4 || c->mx4))
         return set_err(5, "config.json: quant_method %s with model_type "
                           "gemma3 is not supported (the fp8 and gptq gate-up "
                           "kernels have no GELU form)", qm->str.c_str());
@@ -297,6 +298,49 @@ int parse_config(const char* json, ModelConfig* c) {
           if (p->bool_or(false))
             return set_err(5, "gptq: desc_act true (act-order) is not "
                               "supported");
+      }
+      if (c->mx4) {
+        // AMD Quark MXFP4: global_quant_config.weight (an object, or a list
+        // of one) = fp4 / per_group / 32 / e8m0 along K.  `exclude` and the
+        // input_tensors / output_tensors entries are ignored.
+        const char* G = "quark: global_quant_config.weight";
+        auto gq = qc->get("global_quant_config");
+        auto w = gq && gq->kind == minijson::Value::Obj ? gq->get("weight")
+                                                        : nullptr;
+        if (w && w->kind == minijson::Value::Arr && w->arr.size() == 1)
+          w = w->arr[0];
+        if (!w || w->kind != minijson::Value::Obj)
+          return set_err(5, "%s is missing (an object, or a list of one)", G);
+        auto str = [&](const char* k) {
+          auto p = w->get(k);
+          return p && p->kind == minijson::Value::Str ? p->str
+                                                      : std::string("?");
+        };
+        if (str("dtype") != "fp4")
+          return set_err(5, "%s.dtype %s is not supported (only fp4)", G,
+                         str("dtype").c_str());
+        if (str("qscheme") != "per_group")
+          return set_err(5, "%s.qscheme %s is not supported (only per_group)",
+                         G, str("qscheme").c_str());
+        auto gs = w->get("group_size");
+        if (!gs || gs->kind != minijson::Value::Num || gs->num != 32)
+          return set_err(5, "%s.group_size %g is not supported (only 32)", G,
+                         gs && gs->kind == minijson::Value::Num ? gs->num
+                                                                : -1.0);
+        if (str("scale_format") != "e8m0")
+          return set_err(5, "%s.scale_format %s is not supported (only e8m0)",
+                         G, str("scale_format").c_str());
+        if (auto ax = w->get("ch_axis"))
+          if (ax->kind == minijson::Value::Num && ax->num != -1 &&
+              ax->num != 1)
+            return set_err(5, "%s.ch_axis %g is not supported (-1 or 1: the "
+                              "groups run along in_features)", G, ax->num);
+        for (const char* k : {"layer_quant_config", "layer_type_quant_config"})
+          if (auto p = qc->get(k))
+            if ((p->kind == minijson::Value::Obj && !p->obj.empty()) ||
+                (p->kind == minijson::Value::Arr && !p->arr.empty()))
+              return set_err(5, "quark: a non-empty %s (mixed per-layer "
+                                "formats) is not supported", k);
       }
     }
   if (auto rs = v->get("rope_scaling")) {
@@ -403,6 +447,30 @@ int w4_config_err(const ModelConfig& c) {
   if ((r = w4_dim_err("gate_proj/up_proj", I, H, c.grp(H)))) return r;
   if ((r = w4_dim_err("down_proj", H, I, c.grp(I)))) return r;
   return 0;
+}
+
+// mxfp4 shape rules (host only; engine create, the op entries and the dispatch
+// query): a lane's 16-B load is one 32-wide MX block of one row, and the
+// register GEMV covers K <= 32768.  No rule on N: there are no packed zero
+// points.
+int mx4_dim_err(const char* name, int N, int K) {
+  if (K < 32 || K > 32768)
+    return set_err(5, "mxfp4: %s in_features %d outside [32, 32768]", name, K);
+  if (K % 32 != 0)
+    return set_err(5, "mxfp4: %s in_features %d is not a multiple of the "
+                   "block size 32", name, K);
+  if (N < 1) return set_err(5, "mxfp4: %s out_features %d", name, N);
+  return 0;
+}
+int mx4_config_err(const ModelConfig& c) {
+  const int H = c.hidden, I = c.inter, Sq = c.sq();
+  int r;
+  if ((r = mx4_dim_err("q_proj/k_proj/v_proj", c.nqkv(), H))) return r;
+  if ((r = mx4_dim_err("o_proj", H, Sq))) return r;
+  if (H > 16384)
+    return set_err(5, "mxfp4: gate_proj/up_proj in_features %d > 16384", H);
+  if ((r = mx4_dim_err("gate_proj/up_proj", 2 * I, H))) return r;
+  return mx4_dim_err("down_proj", H, I);
 }
 
 // ---------------------------------------------------------------------------
@@ -600,6 +668,21 @@ static void enqueue_norm_proj(cake_engine* e, const Proj& p, const u16* nw,
   const float eps = e->c.rms_eps;
   const double flops = 2.0 * N * K, out_bytes = (gateup ? I : N) * 2;
   auto norm = [&] { launch_rmsnorm(e->x, nw, e->xn, 1, K, eps, e->stream); };
+  if (p.fmt == W_MXFP4) {  // the gptq route: split norm, then the GEMV
+    {
+      StatScope ss(e, "rmsnorm", 2.0 * K * 2, 0);
+      norm();
+    }
+    StatScope ss(e, gateup ? "gemv_gateup_mx4" : "gemv_mx4",
+                 p.bytes() + K * 2 + out_bytes, flops);
+    if (gateup)
+      launch_gemv_gateup_mx4(p.w4(), p.mx_scales(), e->xn, out, I, K,
+                             e->stream);
+    else
+      launch_gemv_mx4(p.w4(), p.mx_scales(), e->xn, out, nullptr, N, K, 0,
+                      e->stream);
+    return;
+  }
   if (p.fmt == W_GPTQ) {
     {
       StatScope ss(e, "rmsnorm", 2.0 * K * 2, 0);
@@ -658,9 +741,13 @@ static void enqueue_norm_proj(cake_engine* e, const Proj& p, const u16* nw,
 static void enqueue_res_proj(cake_engine* e, const Proj& p, const char* fam,
                              const u16* a, int slot) {
   const int N = p.N, K = p.K;
-  StatScope ss(e, p.fmt == W_GPTQ ? "gemv_w4" : fam,
+  StatScope ss(e, p.fmt == W_GPTQ    ? "gemv_w4"
+                  : p.fmt == W_MXFP4 ? "gemv_mx4"
+                                     : fam,
                p.bytes() + K * 2 + N * 4, 2.0 * N * K);
-  if (p.fmt == W_GPTQ) {
+  if (p.fmt == W_MXFP4) {
+    launch_gemv_mx4(p.w4(), p.mx_scales(), a, e->x, e->x, N, K, 1, e->stream);
+  } else if (p.fmt == W_GPTQ) {
     launch_gemv_w4(p.w4(), p.aux, a, e->x, e->x, N, K, p.g, 1, e->stream);
   } else if (p.fmt == W_FP8) {
     NormIO nio{};
@@ -702,6 +789,10 @@ static const u16* gemm_weight(cake_engine* e, const Proj& p) {
   if (p.fmt == W_FP8) {
     StatScope ss(e, "dequant_fp8", io, 0);
     launch_dequant_fp8(p.fp8(), p.aux, e->wscratch, p.N, p.K, e->stream);
+  } else if (p.fmt == W_MXFP4) {
+    StatScope ss(e, "dequant_mx4", io, 0);
+    launch_dequant_mx4(p.w4(), p.mx_scales(), e->wscratch, p.N, p.K,
+                       e->stream);
   } else {
     StatScope ss(e, "dequant_w4", io, 0);
     launch_dequant_w4(p.w4(), p.aux, e->wscratch, p.N, p.K, p.g, e->stream);
@@ -927,7 +1018,7 @@ static int alloc_proj(cake_engine* e, Proj* p, int N, int K) {
   const ModelConfig& c = e->c;
   p->N = N;
   p->K = K;
-  p->fmt = c.fp8 ? W_FP8 : c.w4 ? W_GPTQ : W_BF16;
+  p->fmt = c.fp8 ? W_FP8 : c.w4 ? W_GPTQ : c.mx4 ? W_MXFP4 : W_BF16;
   p->g = c.w4 ? c.grp(K) : 0;
   ALLOC(e->mem, p->w, char, p->w_bytes());
   if (p->aux_elems()) ALLOC(e->mem, p->aux, float, p->aux_elems());
@@ -953,6 +1044,7 @@ static int engine_build(const char* config_json, int layer_lo, int layer_hi,
   if (c.hidden % 8 || c.inter % 8)
     return set_err(5, "hidden/intermediate must be multiples of 8");
   if (c.w4 && (r = w4_config_err(c))) return r;
+  if (c.mx4 && (r = mx4_config_err(c))) return r;
   if (max_seq <= 0) max_seq = c.max_pos;
   max_seq = (max_seq + 31) & ~31;  // MFMA prefill reads whole 32-pos tiles
   if (max_batch_tokens <= 0) max_batch_tokens = 2048;
@@ -1050,7 +1142,7 @@ static int engine_build(const char* config_json, int layer_lo, int layer_hi,
   ALLOC(e->mem, e->attn_out, u16, (size_t)BT * Sq);
   ALLOC(e->mem, e->gu, u16, (size_t)BT * 2 * I);
   ALLOC(e->mem, e->act, u16, (size_t)BT * I);
-  if (c.fp8 || c.w4) {  // holds the largest dequantized projection
+  if (c.fp8 || c.w4 || c.mx4) {  // holds the largest dequantized projection
     const LayerDev& l = e->L[0];
     ALLOC(e->mem, e->wscratch, u16,
           std::max(std::max(l.qkv.elems(), l.o.elems()),

@@ -77,6 +77,8 @@ struct ModelConfig {
   bool w4 = false;   // quant_method == "gptq", bits 4 (gptq.rs:69-86)
   int group = 128;   // gptq group_size; -1 = one group per row
   int grp(int K) const { return group > 0 ? group : K; }
+  bool mx4 = false;  // quant_method == "quark", MXFP4 weights (e2m1 elements,
+                     // one e8m0 scale per 32 along K), run weight-only
   // llama3 rope scaling (config.rs:50-65)
   bool rope_llama3 = false;
   float rs_factor = 1, rs_low = 1, rs_high = 4;
@@ -106,13 +108,16 @@ int parse_config(const char* json, ModelConfig* c);
 // queries)
 int w4_dim_err(const char* name, int N, int K, int g);
 int w4_config_err(const ModelConfig& c);
+// mxfp4 shape rules (kernels_mx4.hip): K % 32 == 0, 32 <= K <= 32768, N >= 1
+int mx4_dim_err(const char* name, int N, int K);
+int mx4_config_err(const ModelConfig& c);
 
 // Full-rotation models without qk-norm and without fp8/4-bit weights take the
 // fused rms_norm -> qkv GEMV -> rope -> KV-store kernel (the QK-norm rows
 // exist exactly when c.qk_norm; qwen2 takes its biased twin, partial rotary
 // the _pr form).  Shared by enqueue_layer_decode and cake_hip_decode_dispatch.
 inline bool fused_qkv_rope_applies(const ModelConfig& c) {
-  return !c.fp8 && !c.w4 && !c.qk_norm && c.hd() % 4 == 0 &&
+  return !c.fp8 && !c.w4 && !c.mx4 && !c.qk_norm && c.hd() % 4 == 0 &&
          c.nqkv() % 4 == 0 && c.rd() % 4 == 0 && (c.hd() - c.rd()) % 4 == 0;
 }
 
@@ -120,32 +125,42 @@ inline bool fused_qkv_rope_applies(const ModelConfig& c) {
 // one projection's weights: y (N) = W (N, K) x (K).  Alloc, load, random init
 // and every launch read format and sizes from here.
 // ---------------------------------------------------------------------------
-enum WFmt { W_BF16, W_FP8, W_GPTQ };
+enum WFmt { W_BF16, W_FP8, W_GPTQ, W_MXFP4 };
 struct Proj {
   int N = 0, K = 0;  // output rows, input width
   WFmt fmt = W_BF16;
   int g = 0;          // gptq: group size along K (c.grp(K)); else 0
   void* w = nullptr;  // bf16 (N, K) | e4m3fn bytes (N, K), fp8.rs:42-64 |
                       // gptq nibbles, out-major, K/8 words per row
-                      // (kernels_w4.hip)
+                      // (kernels_w4.hip) | mxfp4: the checkpoint's (N, K/2)
+                      // bytes, the same words (kernels_mx4.hip)
   float* aux = nullptr;  // fp8: blockwise 128x128 scale_inv (N/128, K/128) |
-                         // gptq: per row (N, K/g) pairs {s, -(z+1)*s}
+                         // gptq: per row (N, K/g) pairs {s, -(z+1)*s} |
+                         // mxfp4: (N, K/32) e8m0 bytes (mx_scales())
   u16* bf16() const { return (u16*)w; }
   unsigned char* fp8() const { return (unsigned char*)w; }
   u32* w4() const { return (u32*)w; }
+  unsigned char* mx_scales() const { return (unsigned char*)aux; }
+  size_t mx_scale_bytes() const { return (size_t)N * (K / 32); }
   size_t elems() const { return (size_t)N * K; }
   size_t w_bytes() const {
     return fmt == W_BF16 ? elems() * 2 : fmt == W_FP8 ? elems() : elems() / 2;
   }
+  // f32 words of aux (mxfp4: its scale bytes, rounded up to whole words)
   size_t aux_elems() const {
-    return fmt == W_FP8    ? (size_t)(N / 128) * (K / 128)
-           : fmt == W_GPTQ ? (size_t)N * (K / g) * 2
-                           : 0;
+    return fmt == W_FP8     ? (size_t)(N / 128) * (K / 128)
+           : fmt == W_GPTQ  ? (size_t)N * (K / g) * 2
+           : fmt == W_MXFP4 ? (mx_scale_bytes() + 3) / 4
+                            : 0;
   }
   // algorithmic bytes of one pass over the weights, as the stats book them
-  // (gptq counts its pairs, fp8 does not count its scales)
+  // (gptq counts its pairs and mxfp4 its scale bytes, fp8 does not count its
+  // scales)
   double bytes() const {
-    return (double)w_bytes() + (fmt == W_GPTQ ? aux_elems() * 4.0 : 0.0);
+    return (double)w_bytes() +
+           (fmt == W_GPTQ    ? aux_elems() * 4.0
+            : fmt == W_MXFP4 ? (double)mx_scale_bytes()
+                             : 0.0);
   }
 };
 

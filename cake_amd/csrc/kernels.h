@@ -108,6 +108,25 @@ void launch_gemv_gateup_w4(const u32* W, const float* sz, const u16* x,
 void launch_dequant_w4(const u32* W, const float* sz, u16* out, int N, int K,
                        int group, hipStream_t s);
 void launch_fill_random_u32(u32* out, size_t n, uint64_t seed, hipStream_t s);
+// MXFP4 family (kernels_mx4.hip).  W: the checkpoint's (N, K/2) bytes read as
+// K/8 words per row; sc: (N, K/32) E8M0 bytes.  K % 32 == 0, 32 <= K <= 32768,
+// any N >= 1; 4 rows per block.  epi as above; x is already normalized.
+// dot2_override: 0 f32 converts + fma, 1 bf16 converts + dot2, -1 =
+// gemv_mx4_dot2_policy.
+int gemv_mx4_kb(int K);  // 4096-wide k blocks: 1 (two half-block rows) |2|4|8
+int gemv_mx4_dot2_policy();
+void launch_gemv_mx4(const u32* W, const unsigned char* sc, const u16* x,
+                     u16* out, const u16* res, int N, int K, int epi,
+                     hipStream_t s, int dot2_override = -1);
+// 4 channels per block; K <= 16384
+void launch_gemv_gateup_mx4(const u32* W, const unsigned char* sc,
+                            const u16* x, u16* out, int I, int K,
+                            hipStream_t s, int dot2_override = -1);
+void launch_dequant_mx4(const u32* W, const unsigned char* sc, u16* out, int N,
+                        int K, hipStream_t s);
+// E8M0 bytes in {base - 1, base, base + 1} by a hash of (seed, index)
+void launch_fill_scale_mx4(unsigned char* out, size_t n, uint64_t seed,
+                           int base, hipStream_t s);
 void launch_embed_token(const u16* embed, const u32* tok, u16* x, int H,
                         hipStream_t s, float* nscale = nullptr,
                         float eps = 1e-5f);

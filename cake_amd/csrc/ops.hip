@@ -955,6 +955,124 @@ extern "C" int cake_hip_op_dequant_w4(int N, int K, int group,
   return ob_down16(b, dout, n + OPG, out);
 }
 
+// ---- mxfp4 op entries: tensors in CHECKPOINT layout, which is the device
+// layout (weight U8 (N, K/2), weight_scale U8 (N, K/32))
+static int mx4_op_args(const char* who, int N, int K, int dot2,
+                       const uint8_t* weight, const uint8_t* scale,
+                       const void* out) {
+  int r = mx4_dim_err(who, N, K);
+  if (r) return r;
+  if (!weight || !scale || !out)
+    return set_err(5, "%s: weight, weight_scale and out are required", who);
+  if (dot2 < -1 || dot2 > 1)
+    return set_err(5, "%s: dot2 %d not in {-1,0,1}", who, dot2);
+  for (size_t i = 0; i < (size_t)N * (K / 32); ++i)
+    if (scale[i] == 255)
+      return set_err(5, "%s: weight_scale byte 255 (E8M0 NaN) at row %zu, "
+                     "block %zu", who, i / (K / 32), i % (K / 32));
+  return 0;
+}
+static int mx4_op_upload(OpBufs& b, int N, int K, const uint8_t* weight,
+                         const uint8_t* scale, u32** dW, unsigned char** dsc) {
+  void *pw, *ps;
+  int r;
+  if ((r = ob_upf32(b, weight, (size_t)N * (K / 2), &pw))) return r;
+  if ((r = ob_upf32(b, scale, (size_t)N * (K / 32), &ps))) return r;
+  *dW = (u32*)pw;
+  *dsc = (unsigned char*)ps;
+  return 0;
+}
+
+extern "C" int cake_hip_op_gemv_mx4(int N, int K, int epi, int dot2,
+                                    int alias, int repeats, const float* x,
+                                    const uint8_t* weight,
+                                    const uint8_t* weight_scale,
+                                    const float* res, float* out,
+                                    int device) {
+  const char* who = "op_gemv_mx4";
+  int r = mx4_op_args(who, N, K, dot2, weight, weight_scale, out);
+  if (r) return r;
+  if (!x) return set_err(5, "%s: x is required", who);
+  if (repeats < 1 || repeats > 16)
+    return set_err(5, "%s: repeats %d outside [1,16]", who, repeats);
+  if (epi < 0 || epi > 1) return set_err(5, "%s: epi %d", who, epi);
+  if ((epi == 1) != (res != nullptr))
+    return set_err(5, "%s: res goes with epi 1", who);
+  if (alias && epi != 1)
+    return set_err(5, "%s: alias needs the residual epilogue", who);
+  OpBufs b;
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreate(&b.s));
+  const size_t ld = (size_t)N + OPG;  // out row stride per repeat
+  u16 *dx, *dres = nullptr, *dout = nullptr;
+  u32* dW;
+  unsigned char* dsc;
+  if ((r = ob_up16(b, x, (size_t)repeats * K, &dx))) return r;
+  if ((r = mx4_op_upload(b, N, K, weight, weight_scale, &dW, &dsc))) return r;
+  if ((r = ob_sent16(b, repeats * ld, &dout))) return r;
+  if (res) {
+    // residual rows at the out stride, so alias can copy them in place
+    std::vector<float> h(repeats * ld, CAKE_HIP_OP_SENTINEL);
+    for (int i = 0; i < repeats; ++i)
+      memcpy(h.data() + i * ld, res + (size_t)i * N, sizeof(float) * N);
+    if ((r = ob_up16(b, h.data(), h.size(), &dres))) return r;
+    HIP_TRY(hipStreamSynchronize(b.s));
+    if (alias) dout = dres;  // out == res, as the engine does with e->x
+  }
+  for (int i = 0; i < repeats; ++i)
+    launch_gemv_mx4(dW, dsc, dx + (size_t)i * K, dout + i * ld,
+                    dres ? dres + i * ld : nullptr, N, K, epi, b.s, dot2);
+  HIP_TRY(hipGetLastError());
+  return ob_down16(b, dout, repeats * ld, out);
+}
+
+extern "C" int cake_hip_op_gemv_gateup_mx4(int I, int K, int dot2,
+                                           const float* x,
+                                           const uint8_t* weight,
+                                           const uint8_t* weight_scale,
+                                           float* out, int device) {
+  const char* who = "op_gemv_gateup_mx4";
+  if (I < 1) return set_err(5, "%s: I %d", who, I);
+  int r = mx4_op_args(who, 2 * I, K, dot2, weight, weight_scale, out);
+  if (r) return r;
+  if (K > 16384)
+    return set_err(5, "%s: K must be <= 16384 (got %d)", who, K);
+  if (!x) return set_err(5, "%s: x is required", who);
+  OpBufs b;
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreate(&b.s));
+  u16 *dx, *dout;
+  u32* dW;
+  unsigned char* dsc;
+  if ((r = ob_up16(b, x, K, &dx))) return r;
+  if ((r = mx4_op_upload(b, 2 * I, K, weight, weight_scale, &dW, &dsc)))
+    return r;
+  if ((r = ob_sent16(b, (size_t)I + OPG, &dout))) return r;
+  launch_gemv_gateup_mx4(dW, dsc, dx, dout, I, K, b.s, dot2);
+  HIP_TRY(hipGetLastError());
+  return ob_down16(b, dout, (size_t)I + OPG, out);
+}
+
+extern "C" int cake_hip_op_dequant_mx4(int N, int K, const uint8_t* weight,
+                                       const uint8_t* weight_scale,
+                                       float* out, int device) {
+  const char* who = "op_dequant_mx4";
+  int r = mx4_op_args(who, N, K, -1, weight, weight_scale, out);
+  if (r) return r;
+  OpBufs b;
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreate(&b.s));
+  const size_t n = (size_t)N * K;
+  u32* dW;
+  unsigned char* dsc;
+  u16* dout;
+  if ((r = mx4_op_upload(b, N, K, weight, weight_scale, &dW, &dsc))) return r;
+  if ((r = ob_sent16(b, n + OPG, &dout))) return r;
+  launch_dequant_mx4(dW, dsc, dout, N, K, b.s);
+  HIP_TRY(hipGetLastError());
+  return ob_down16(b, dout, n + OPG, out);
+}
+
 extern "C" int cake_hip_op_silu_mul_rows(int S, int I, const float* gu,
                                          float* out, int device) {
   const char* who = "op_silu_mul_rows";
@@ -1012,7 +1130,11 @@ extern "C" int cake_hip_op_rms_norm_rows(int outer, int inner,
 // out[i] = {family, rows, KB} for i = qkv, o, gate-up, down, head.  The
 // opt-in split-K residual GEMV (CAKE_GEMV_SPLITK) is not reflected.
 static void plain_dispatch(int N, int K, int quant, int* o) {
-  if (quant == 2) {  // gptq 4-bit: one register family, K <= 32768
+  if (quant == 3) {  // mxfp4: one register family, 4 rows, K <= 32768
+    o[0] = CAKE_HIP_FAM_GEMV_MX4;
+    o[1] = 4;
+    o[2] = gemv_mx4_kb(K);
+  } else if (quant == 2) {  // gptq 4-bit: one register family, K <= 32768
     o[0] = CAKE_HIP_FAM_GEMV_W4;
     o[1] = gemv_w4_rows_policy(N, K);
     o[2] = gemv_w4_kb(K);
@@ -1033,7 +1155,8 @@ extern "C" int cake_hip_decode_dispatch(const char* config_json,
   if (r) return r;
   const int H = c.hidden, I = c.inter;
   if (c.w4 && (r = w4_config_err(c))) return r;
-  const int quant = c.w4 ? 2 : c.fp8 ? 1 : 0;
+  if (c.mx4 && (r = mx4_config_err(c))) return r;
+  const int quant = c.mx4 ? 3 : c.w4 ? 2 : c.fp8 ? 1 : 0;
   if (fused_qkv_rope_applies(c)) {
     out[0] = CAKE_HIP_FAM_QKV_ROPE;
     out[1] = 4;
@@ -1042,12 +1165,16 @@ extern "C" int cake_hip_decode_dispatch(const char* config_json,
     plain_dispatch(c.nqkv(), H, quant, out);
   }
   plain_dispatch(H, c.sq(), quant, out + 3);
-  out[6] = c.w4       ? CAKE_HIP_FAM_GATEUP_W4
+  out[6] = c.mx4      ? CAKE_HIP_FAM_GATEUP_MX4
+           : c.w4     ? CAKE_HIP_FAM_GATEUP_W4
            : c.fp8    ? CAKE_HIP_FAM_GATEUP_FP8
            : c.gemma3 ? CAKE_HIP_FAM_GATEUP_GELU
                       : CAKE_HIP_FAM_GATEUP;
-  out[7] = c.w4 || c.fp8 ? 4 : gemv_gateup_rows_policy();
-  out[8] = c.w4 ? gemv_w4_kb(H) : c.fp8 ? gemv_fp8_kb(H) : gemv_kb(H);
+  out[7] = c.mx4 || c.w4 || c.fp8 ? 4 : gemv_gateup_rows_policy();
+  out[8] = c.mx4   ? gemv_mx4_kb(H)
+           : c.w4  ? gemv_w4_kb(H)
+           : c.fp8 ? gemv_fp8_kb(H)
+                   : gemv_kb(H);
   plain_dispatch(H, I, quant, out + 9);
   plain_dispatch(c.vocab, H, 0, out + 12);  // lm_head stays bf16
   return 0;

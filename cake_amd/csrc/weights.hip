@@ -1,6 +1,6 @@
 // Weights of the cake_hip engine: the safetensors loader (single file,
-// sharded index or directory; split and fused checkpoints; bf16, fp8 and
-// gptq projections) and cake_hip_init_random.  Both walk a layer's four Proj
+// sharded index or directory; split and fused checkpoints; bf16, fp8, gptq
+// and mxfp4 projections) and cake_hip_init_random.  Both walk a layer's four Proj
 // records (engine_internal.h) and take format and sizes from them.
 #include <algorithm>
 #include <cstdio>
@@ -378,6 +378,40 @@ static int load_safetensors_file(cake_engine* e, const char* path) {
                       hipMemcpyHostToDevice));
     return 0;
   };
+  // mxfp4 tensors P.weight U8 (rows, K/2) and P.weight_scale U8 (rows, K/32)
+  // -> rows [row0, row0 + rows) of p as they are: the checkpoint layout is the
+  // device layout (kernels_mx4.hip).  A scale byte 255 (E8M0 NaN) is refused.
+  auto load_mx4 = [&](const std::string& P, const Proj& p, size_t row0,
+                      size_t rows) -> int {
+    StTensor tw, ts;
+    int rr = need(P + ".weight", &tw);
+    if (rr == -1) return 0;  // lives in another shard, with its scales
+    if (rr) return rr;
+    rr = need(P + ".weight_scale", &ts);
+    if (rr == -1)
+      return set_err(4, "%s.weight_scale must be in the same file as "
+                        "%s.weight", P.c_str(), P.c_str());
+    if (rr) return rr;
+    const size_t K = p.K;
+    auto bad = [&](const char* suf, const StTensor& s, size_t b) {
+      return set_err(5, "%s%s: %s (%s), expected U8 (%zu, %zu)", P.c_str(),
+                     suf, s.dtype.c_str(), s.shape_str().c_str(), rows, b);
+    };
+    if (tw.dtype != "U8" || !tw.is2d(rows, K / 2))
+      return bad(".weight", tw, K / 2);
+    if (ts.dtype != "U8" || !ts.is2d(rows, K / 32))
+      return bad(".weight_scale", ts, K / 32);
+    const unsigned char* sb = (const unsigned char*)(base + ts.off0);
+    for (size_t i = 0; i < rows * (K / 32); ++i)
+      if (sb[i] == 255)
+        return set_err(5, "%s.weight_scale: byte 255 (E8M0 NaN) at row %zu, "
+                          "block %zu", P.c_str(), i / (K / 32), i % (K / 32));
+    HIP_TRY(hipMemcpy(p.fp8() + row0 * (K / 2), base + tw.off0,
+                      rows * (K / 2), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(p.mx_scales() + row0 * (K / 32), sb, rows * (K / 32),
+                      hipMemcpyHostToDevice));
+    return 0;
+  };
   // The text model's tensor prefix.  A gemma3 checkpoint saved from the
   // multimodal class nests it (and carries vision tensors, which nothing
   // here asks for): the first candidate any tensor of this file starts with.
@@ -462,6 +496,9 @@ static int load_safetensors_file(cake_engine* e, const char* path) {
         if (pj.fmt == W_GPTQ) {
           int r = load_w4(P, pj, pt.row0, pt.rows);
           if (r) return r;
+        } else if (pj.fmt == W_MXFP4) {
+          int r = load_mx4(P, pj, pt.row0, pt.rows);
+          if (r) return r;
         } else if (pj.fmt == W_FP8) {
           LOADW(P + ".weight", upload_weight_u8(e, pj.fp8() + pt.row0 * K, base, t, pt.rows * K));
         } else {
@@ -524,6 +561,16 @@ extern "C" int cake_hip_init_random(cake_engine* e, uint64_t seed,
     host.resize(n);
     if (p.fmt == W_BF16) {
       launch_fill_random(p.bf16(), p.elems(), s, scale, e->stream);
+      return;
+    }
+    if (p.fmt == W_MXFP4) {
+      // random e2m1 codes (rms 2.93) under scale bytes in a three-wide band
+      // (rms factor 1.32) around 2^round(log2(0.15 * scale)): weights of rms
+      // about 0.58 * scale, the bf16 init's uniform(+-scale)
+      launch_fill_random_u32(p.w4(), p.elems() / 8, s, e->stream);
+      const int b = 127 + (int)lroundf(log2f(0.15f * scale));
+      launch_fill_scale_mx4(p.mx_scales(), p.mx_scale_bytes(), s ^ 0x5ca1eull,
+                            std::min(253, std::max(2, b)), e->stream);
       return;
     }
     if (p.fmt == W_FP8) {

@@ -370,6 +370,31 @@ int cake_hip_op_gemv_gateup_w4(int I, int K, int group, int rows,
 int cake_hip_op_dequant_w4(int N, int K, int group, const int32_t *qweight,
                            const int32_t *qzeros, const float *scales,
                            float *out, int device);
+/* MXFP4 op entries.  The tensors are in CHECKPOINT layout, which is also the
+ * device layout: weight (N, K/2) bytes, byte b of a row = e2m1 codes of
+ * k = 2b (low nibble) and k = 2b + 1 (high nibble); weight_scale (N, K/32)
+ * E8M0 bytes, W[j, k] = e2m1(code) * 2^(s - 127).  Rules (error 5):
+ * K % 32 == 0, 32 <= K <= 32768, N >= 1, no scale byte 255.
+ * gemv_mx4: epi 0 bf16 out, 1 bf16 out + res; dot2 -1 (policy) | 0 (f32
+ * converts + fma) | 1 (bf16 converts + dot2); alias: out == res; the kernel is
+ * launched `repeats` (1..16) times, repeat i on x row i and res row i; out is
+ * (repeats, N + CAKE_HIP_OP_GUARD). */
+int cake_hip_op_gemv_mx4(int N, int K, int epi, int dot2, int alias,
+                         int repeats, const float *x, const uint8_t *weight,
+                         const uint8_t *weight_scale, const float *res,
+                         float *out, int device);
+/* out[c] = silu(g_c) * u_c over one fused tensor of 2I rows (gate rows
+ * [0, I), up rows [I, 2I)); x is already normalized.  K <= 16384.  out is
+ * (I + CAKE_HIP_OP_GUARD). */
+int cake_hip_op_gemv_gateup_mx4(int I, int K, int dot2, const float *x,
+                                const uint8_t *weight,
+                                const uint8_t *weight_scale, float *out,
+                                int device);
+/* MXFP4 -> bf16 (N, K) row-major, as the prefill path dequantizes into its
+ * scratch; out is (N*K + CAKE_HIP_OP_GUARD). */
+int cake_hip_op_dequant_mx4(int N, int K, const uint8_t *weight,
+                            const uint8_t *weight_scale, float *out,
+                            int device);
 /* Prefill silu_mul over S rows of gu (S, 2I) = [gate | up]: out[s, c] =
  * silu(gu[s, c]) * gu[s, I + c]; I % 8 == 0.  out is
  * (S*I + CAKE_HIP_OP_GUARD). */
@@ -403,6 +428,8 @@ enum {
   CAKE_HIP_FAM_GEMV_W4 = 9,
   CAKE_HIP_FAM_GATEUP_W4 = 10,
   CAKE_HIP_FAM_GATEUP_GELU = 11, /* gemma3: the GELU-tanh twin of GATEUP */
+  CAKE_HIP_FAM_GEMV_MX4 = 12,
+  CAKE_HIP_FAM_GATEUP_MX4 = 13,
 };
 /* fp8 is the quant selector: 0 bf16, 1 fp8.  The 4-bit (gptq) kernels need a
  * group size and are queried through cake_hip_linear_dispatch_w4. */
