@@ -129,6 +129,14 @@ def _load_lib():
                                                  c]
     lib.cake_hip_op_gelu_mul_rows.argtypes = [c, c, fp, fp, c]
     lib.cake_hip_op_embed_scaled.argtypes = [c, c, c, c, fp, u32p, fp, c]
+    lib.cake_hip_op_kv8_quant.argtypes = [c] * 5 + [fp] * 3 + [u8p, u8p, fp,
+                                                                fp, c]
+    lib.cake_hip_op_kv8_dequant.argtypes = [c] * 4 + [u8p, u8p] + [fp] * 5 + \
+        [c]
+    lib.cake_hip_op_attn_decode_kv8.argtypes = [c] * 7 + [fp, u8p, u8p] + \
+        [fp] * 3 + [c]
+    lib.cake_hip_kv_dispatch.argtypes = [cp, c,
+                                         ctypes.POINTER(ctypes.c_int64)]
     lib.cake_hip_sync.argtypes = [p]
     return lib
 
@@ -331,6 +339,85 @@ def op_attn_decode(q, kc, vc, pos, window=0, nchunk=8, repeats=1, device=0):
         nh, nkv, hd, max_seq, pos, window, nchunk, repeats, qp, kp, vp,
         out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), device))
     return out
+
+
+# ---- fp8 (e4m3) KV cache, head_dim 128 --------------------------------------
+def op_kv8_quant(kc, vc, vtc, k8, v8, ks, vs, pos0, S, decode=False,
+                 device=0):
+    """The quantizing KV store on rows [pos0, pos0+S) of the bf16 scratch
+    images kc / vc (nkv, max_seq, 128) and vtc (nkv, 128, max_seq): writes the
+    rows' e4m3 codes into k8 / v8 (nkv, max_seq, 128) u8 and scales into ks /
+    vs (nkv, max_seq), and code * scale back over the scratch rows.  Every
+    buffer goes in as given and comes back; rows outside the range must come
+    back untouched.  decode=True (S == 1) reads the position from device
+    memory.  Returns (kc, vc, vtc, k8, v8, ks, vs)."""
+    kc = np.array(kc, dtype=np.float32)
+    nkv, max_seq = kc.shape[0], kc.shape[1]
+    vc, vtc = np.array(vc, dtype=np.float32), np.array(vtc, dtype=np.float32)
+    k8, v8 = np.array(k8, dtype=np.uint8), np.array(v8, dtype=np.uint8)
+    ks, vs = np.array(ks, dtype=np.float32), np.array(vs, dtype=np.float32)
+    ptr = [_f32_shaped(kc, (nkv, max_seq, 128), "kc")[1],
+           _f32_shaped(vc, (nkv, max_seq, 128), "vc")[1],
+           _f32_shaped(vtc, (nkv, 128, max_seq), "vtc")[1],
+           _u8(k8, (nkv, max_seq, 128), "k8")[1],
+           _u8(v8, (nkv, max_seq, 128), "v8")[1],
+           _f32_shaped(ks, (nkv, max_seq), "ks")[1],
+           _f32_shaped(vs, (nkv, max_seq), "vs")[1]]
+    _check(_lib.cake_hip_op_kv8_quant(int(S), int(pos0), int(bool(decode)),
+                                      nkv, max_seq, *ptr, device))
+    return kc, vc, vtc, k8, v8, ks, vs
+
+
+def op_kv8_dequant(k8, v8, ks, vs, kc, vc, vtc, lo, p0, device=0):
+    """Rows [lo, p0) of the scratch images kc / vc / vtc (given, returned) =
+    code * scale from k8 / v8 / ks / vs.  Returns (kc, vc, vtc)."""
+    kc = np.array(kc, dtype=np.float32)
+    nkv, max_seq = kc.shape[0], kc.shape[1]
+    vc, vtc = np.array(vc, dtype=np.float32), np.array(vtc, dtype=np.float32)
+    _, k8p = _u8(k8, (nkv, max_seq, 128), "k8")
+    _v, v8p = _u8(v8, (nkv, max_seq, 128), "v8")
+    _s, ksp = _f32_shaped(ks, (nkv, max_seq), "ks")
+    _t, vsp = _f32_shaped(vs, (nkv, max_seq), "vs")
+    _check(_lib.cake_hip_op_kv8_dequant(
+        int(lo), int(p0), nkv, max_seq, k8p, v8p, ksp, vsp,
+        _f32_shaped(kc, (nkv, max_seq, 128), "kc")[1],
+        _f32_shaped(vc, (nkv, max_seq, 128), "vc")[1],
+        _f32_shaped(vtc, (nkv, 128, max_seq), "vtc")[1], device))
+    return kc, vc, vtc
+
+
+def op_attn_decode_kv8(q, k8, v8, ks, vs, pos, window=0, nchunk=8, repeats=1,
+                       device=0):
+    """op_attn_decode over an fp8 cache: q (nh, 128), codes k8 / v8 (nkv,
+    max_seq, 128) u8 and row scales ks / vs (nkv, max_seq), read as given.
+    Returns (repeats, nh*128)."""
+    q = np.ascontiguousarray(q, dtype=np.float32)
+    nh = q.shape[0]
+    k8 = np.ascontiguousarray(k8, dtype=np.uint8)
+    nkv, max_seq = k8.shape[0], k8.shape[1]
+    _, qp = _f32_shaped(q, (nh, 128), "q")
+    _k, k8p = _u8(k8, (nkv, max_seq, 128), "k8")
+    _v, v8p = _u8(v8, (nkv, max_seq, 128), "v8")
+    _s, ksp = _f32_shaped(ks, (nkv, max_seq), "ks")
+    _t, vsp = _f32_shaped(vs, (nkv, max_seq), "vs")
+    out = np.empty((max(repeats, 0), nh * 128), dtype=np.float32)
+    _check(_lib.cake_hip_op_attn_decode_kv8(
+        nh, nkv, max_seq, pos, window, nchunk, repeats, qp, k8p, v8p, ksp,
+        vsp, out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), device))
+    return out
+
+
+def kv_dispatch(config, max_seq=0):
+    """The KV-cache plan of engine create (host only): dict(format ("bf16" |
+    "fp8_e4m3", the config's kv_cache_dtype), layer_bytes (KV bytes per
+    layer), scratch_bytes (the engine-wide bf16 scratch of an fp8 cache),
+    group (q-heads per decode-attention block), grid_y)."""
+    if isinstance(config, dict):
+        config = json.dumps(config)
+    o = (ctypes.c_int64 * 5)()
+    _check(_lib.cake_hip_kv_dispatch(config.encode(), int(max_seq), o))
+    return dict(format=("bf16", "fp8_e4m3")[o[0]], layer_bytes=o[1],
+                scratch_bytes=o[2], group=o[3], grid_y=o[4])
 
 
 def op_sample(logits, temperature, top_k=0, top_p=1.0, repeat_penalty=1.0,
@@ -951,9 +1038,14 @@ def comm_id() -> bytes:
 # ---------------------------------------------------------------------------
 class Engine:
     def __init__(self, config, layer_lo=0, layer_hi=None, flags=None,
-                 max_seq=0, max_batch_tokens=0, device=0):
+                 max_seq=0, max_batch_tokens=0, device=0, kv_dtype=None):
+        """kv_dtype: None = what the config says (kv_cache_dtype, default
+        "bf16"); "bf16" | "fp8_e4m3" overrides it."""
         if isinstance(config, dict):
             config = json.dumps(config)
+        if kv_dtype is not None:
+            config = json.dumps({**json.loads(config),
+                                 "kv_cache_dtype": kv_dtype})
         cfg = json.loads(config)
         if cfg.get("model_type") == "gemma3":
             # the multimodal form: the text model's fields, HF's defaults

@@ -359,6 +359,15 @@ int parse_config(const char* json, ModelConfig* c) {
   }
   if (!c->hidden || !c->vocab || !c->layers || !c->nh)
     return set_err(5, "config.json: missing required fields");
+  if (auto p = root->get("kv_cache_dtype"))
+    if (!p->is_null()) {
+      if (p->kind != minijson::Value::Str ||
+          (p->str != "bf16" && p->str != "fp8_e4m3"))
+        return set_err(5, "config.json: kv_cache_dtype %s is not supported "
+                          "(bf16 or fp8_e4m3)",
+                       p->kind == minijson::Value::Str ? p->str.c_str() : "?");
+      c->kv8 = p->str == "fp8_e4m3";
+    }
   if (c->fused_ckpt && c->fp8)
     return set_err(5, "config.json: quant_method fp8 with model_type phi3 is "
                       "not supported");
@@ -471,6 +480,22 @@ int mx4_config_err(const ModelConfig& c) {
     return set_err(5, "mxfp4: gate_proj/up_proj in_features %d > 16384", H);
   if ((r = mx4_dim_err("gate_proj/up_proj", 2 * I, H))) return r;
   return mx4_dim_err("down_proj", H, I);
+}
+
+// fp8 KV cache (host only; engine create and cake_hip_kv_dispatch): the
+// quantizer and the decode kernel are written for 128-B rows
+int kv8_config_err(const ModelConfig& c) {
+  if (c.kv8 && c.hd() != 128)
+    return set_err(5, "config.json: kv_cache_dtype fp8_e4m3 needs head_dim "
+                      "128 (got head_dim %d)", c.hd());
+  return 0;
+}
+size_t kv_layer_bytes(const ModelConfig& c, int max_seq) {
+  const size_t rows = (size_t)c.nkv * max_seq, elems = rows * c.hd();
+  return c.kv8 ? 2 * elems + 2 * rows * sizeof(float) : 3 * elems * 2;
+}
+size_t kv_scratch_bytes(const ModelConfig& c, int max_seq) {
+  return c.kv8 ? 3 * (size_t)c.nkv * max_seq * c.hd() * 2 : 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -834,7 +859,19 @@ static void enqueue_layer_decode(cake_engine* e, LayerDev& l,
                              e->dev_pos, c.nh, c.nkv, hd, c.rd(), e->max_seq,
                              l.qnorm, l.knorm, c.rms_eps, e->stream, l.bqkv);
   }
-  {  // decode attention over the cache (single launch, split-KV combine)
+  if (c.kv8) {  // the row just stored in the scratch -> codes, then attend
+    {
+      StatScope ss(e, "kv8_quant", 2.0 * c.skv() * (2 + 2 + 1) + c.nkv * 8, 0);
+      launch_kv8_quant(l.kc, l.vc, l.vtc, l.k8, l.v8, l.ks, l.vs, e->dev_pos,
+                       0, 1, c.nkv, e->max_seq, e->stream);
+    }
+    const double n = e->host_pos + 1;
+    StatScope ss(e, "attn_decode_kv8",
+                 2.0 * n * (c.skv() + c.nkv * 4) + Sq * 2 * 2, 4.0 * n * Sq);
+    launch_attn_decode_kv8(e->qkv, l.k8, l.v8, l.ks, l.vs, e->dev_pos,
+                           e->attn_ws, e->attn_cnt, e->attn_out, c.nh, c.nkv,
+                           e->max_seq, e->nchunk, c.win_for(l.idx), e->stream);
+  } else {  // decode attention over the cache (single launch, split-KV combine)
     double kvbytes = 2.0 * (e->host_pos + 1) * c.skv() * 2;
     StatScope ss(e, "attn_decode", kvbytes + Sq * 2 * 2,
                  4.0 * (e->host_pos + 1) * Sq);
@@ -877,6 +914,23 @@ static void enqueue_layer_prefill(cake_engine* e, LayerDev& l, int S,
                               pos0, S, c.nh, c.nkv, hd, c.rd(), e->max_seq,
                               Nq, l.qnorm, l.knorm, c.rms_eps, e->stream,
                               l.bqkv);
+  }
+  if (c.kv8) {
+    // the scratch belongs to whichever layer used it last: refill the rows
+    // this chunk attends to below pos0, then quantize the rows just stored
+    // (and leave their dequantized values in the scratch)
+    const int win = c.win_for(l.idx);
+    const int lo = win > 0 ? std::max(0, pos0 + 1 - win) & ~63 : 0;
+    if (pos0 > lo) {
+      const double rows = (double)(pos0 - lo) * c.nkv;
+      StatScope ss(e, "kv8_dequant", rows * (2.0 * hd * (1 + 3) + 8), 0);
+      launch_kv8_dequant(l.kc, l.vc, l.vtc, l.k8, l.v8, l.ks, l.vs, lo, pos0,
+                         c.nkv, e->max_seq, e->stream);
+    }
+    const double rows = (double)S * c.nkv;
+    StatScope ss(e, "kv8_quant", rows * (2.0 * hd * (2 + 2 + 1) + 8), 0);
+    launch_kv8_quant(l.kc, l.vc, l.vtc, l.k8, l.v8, l.ks, l.vs, nullptr, pos0,
+                     S, c.nkv, e->max_seq, e->stream);
   }
   {
     double n_avg = pos0 + (S + 1) * 0.5;
@@ -1025,6 +1079,24 @@ static int alloc_proj(cake_engine* e, Proj* p, int N, int K) {
   return 0;
 }
 
+// fp8 KV cache, create and reset: codes to zero, scales to 1, scratch to zero
+static int kv8_clear(cake_engine* e) {
+  const size_t rows = (size_t)e->c.nkv * e->max_seq, elems = rows * e->c.hd();
+  for (u16* kv : {e->kv_kc, e->kv_vc, e->kv_vtc})
+    HIP_TRY(hipMemsetAsync(kv, 0, elems * 2, e->stream));
+  for (auto& l : e->L) {
+    HIP_TRY(hipMemsetAsync(l.k8, 0, elems, e->stream));
+    HIP_TRY(hipMemsetAsync(l.v8, 0, elems, e->stream));
+    // 0x3f800000 = 1.0f in every word
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)l.ks, 0x3f800000, rows,
+                              e->stream));
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)l.vs, 0x3f800000, rows,
+                              e->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return 0;
+}
+
 // Builds the engine into *out, which is set as soon as the engine exists:
 // on a failing return the caller frees whatever was built so far.
 static int engine_build(const char* config_json, int layer_lo, int layer_hi,
@@ -1045,6 +1117,7 @@ static int engine_build(const char* config_json, int layer_lo, int layer_hi,
     return set_err(5, "hidden/intermediate must be multiples of 8");
   if (c.w4 && (r = w4_config_err(c))) return r;
   if (c.mx4 && (r = mx4_config_err(c))) return r;
+  if ((r = kv8_config_err(c))) return r;
   if (max_seq <= 0) max_seq = c.max_pos;
   max_seq = (max_seq + 31) & ~31;  // MFMA prefill reads whole 32-pos tiles
   if (max_batch_tokens <= 0) max_batch_tokens = 2048;
@@ -1071,6 +1144,13 @@ static int engine_build(const char* config_json, int layer_lo, int layer_hi,
   for (size_t li = 0; li < e->L.size(); ++li)
     e->L[li].idx = layer_lo + (int)li;
   const size_t kv_elems = (size_t)c.nkv * max_seq * hd;
+  const size_t kv_rows = (size_t)c.nkv * max_seq;
+  if (c.kv8) {  // the one bf16 scratch every layer attends through
+    for (u16** kv : {&e->kv_kc, &e->kv_vc, &e->kv_vtc}) {
+      ALLOC(e->mem, *kv, u16, kv_elems);
+      HIP_TRY(hipMemset(*kv, 0, kv_elems * 2));
+    }
+  }
   for (auto& l : e->L) {
     ALLOC(e->mem, l.rms1, u16, H);
     ALLOC(e->mem, l.rms2, u16, H);
@@ -1089,11 +1169,22 @@ static int engine_build(const char* config_json, int layer_lo, int layer_hi,
     }
     // zero the caches: positions >= n are masked (weight 0) but 0*NaN from
     // allocator garbage would still poison the PV MFMA
+    if (c.kv8) {
+      l.kc = e->kv_kc;
+      l.vc = e->kv_vc;
+      l.vtc = e->kv_vtc;
+      ALLOC(e->mem, l.k8, unsigned char, kv_elems);
+      ALLOC(e->mem, l.v8, unsigned char, kv_elems);
+      ALLOC(e->mem, l.ks, float, kv_rows);
+      ALLOC(e->mem, l.vs, float, kv_rows);
+      continue;
+    }
     for (u16** kv : {&l.kc, &l.vc, &l.vtc}) {
       ALLOC(e->mem, *kv, u16, kv_elems);
       HIP_TRY(hipMemset(*kv, 0, kv_elems * 2));
     }
   }
+  if (c.kv8 && (r = kv8_clear(e))) return r;
   if (e->has_embed()) ALLOC(e->mem, e->embed, u16, (size_t)V * H);
   if (e->has_head()) {
     ALLOC(e->mem, e->norm_w, u16, H);
@@ -1250,6 +1341,12 @@ extern "C" int cake_hip_reset(cake_engine* e) {
   // clear the KV caches (Goodbye semantics, worker.rs:364-384 /
   // cache.rs:248-253)
   const size_t kv_bytes = (size_t)e->c.nkv * e->max_seq * e->c.hd() * 2;
+  if (e->c.kv8) {
+    int r = kv8_clear(e);
+    if (r) return r;
+    e->host_pos = 0;
+    return 0;
+  }
   for (auto& l : e->L) {
     HIP_TRY(hipMemsetAsync(l.kc, 0, kv_bytes, e->stream));
     HIP_TRY(hipMemsetAsync(l.vc, 0, kv_bytes, e->stream));

@@ -79,6 +79,10 @@ struct ModelConfig {
   int grp(int K) const { return group > 0 ? group : K; }
   bool mx4 = false;  // quant_method == "quark", MXFP4 weights (e2m1 elements,
                      // one e8m0 scale per 32 along K), run weight-only
+  // kv_cache_dtype "fp8_e4m3": K and V live as e4m3 codes with one
+  // power-of-two scale per (layer, kv head, position) row (kernels_kv8.hip);
+  // absent or "bf16" = the bf16 cache.  hd 128 only (kv8_config_err).
+  bool kv8 = false;
   // llama3 rope scaling (config.rs:50-65)
   bool rope_llama3 = false;
   float rs_factor = 1, rs_low = 1, rs_high = 4;
@@ -111,6 +115,12 @@ int w4_config_err(const ModelConfig& c);
 // mxfp4 shape rules (kernels_mx4.hip): K % 32 == 0, 32 <= K <= 32768, N >= 1
 int mx4_dim_err(const char* name, int N, int K);
 int mx4_config_err(const ModelConfig& c);
+// fp8 KV cache: head_dim 128 only
+int kv8_config_err(const ModelConfig& c);
+// bytes of one layer's KV cache in the config's format, and of the engine-wide
+// bf16 scratch an fp8 cache attends through in prefill (0 for bf16)
+size_t kv_layer_bytes(const ModelConfig& c, int max_seq);
+size_t kv_scratch_bytes(const ModelConfig& c, int max_seq);
 
 // Full-rotation models without qk-norm and without fp8/4-bit weights take the
 // fused rms_norm -> qkv GEMV -> rope -> KV-store kernel (the QK-norm rows
@@ -180,8 +190,14 @@ struct LayerDev {
   // qwen2: fused q|k|v projection bias, (Nq) f32 in qkv's row order (f32 so
   // that an F16 bias of a GPTQ checkpoint stays exact); null otherwise
   float* bqkv = nullptr;
+  // bf16 cache: this layer's own.  fp8 cache: all three alias the engine's
+  // one shared scratch, which holds whichever layer ran last
   u16 *kc = nullptr, *vc = nullptr;  // (nkv, max_seq, hd) each
   u16 *vtc = nullptr;                // V transposed: (nkv, hd, max_seq)
+  // fp8 cache: e4m3 codes (nkv, max_seq, hd) and f32 row scales (nkv,
+  // max_seq); null otherwise
+  unsigned char *k8 = nullptr, *v8 = nullptr;
+  float *ks = nullptr, *vs = nullptr;
 };
 
 // ---------------------------------------------------------------------------
@@ -229,6 +245,8 @@ struct cake_engine {
   u16 *x = nullptr, *xn = nullptr, *qkv = nullptr, *attn_out = nullptr;
   u16 *gu = nullptr, *act = nullptr;
   u16 *wscratch = nullptr;  // fp8/w4 prefill: per-layer dequantized weight
+  // fp8 KV cache: the shared bf16 scratch (one layer's kc / vc / vtc)
+  u16 *kv_kc = nullptr, *kv_vc = nullptr, *kv_vtc = nullptr;
   float* logits = nullptr;
   float* fbuf = nullptr;
   u32* ids = nullptr;

@@ -174,6 +174,29 @@ int attn_decode_grid_y(int nh, int nkv, int hd);
 // 1 grouped, 2 short-context in-block split-KV (CAKE_ATTN_SHORT=0 -> 1),
 // 3 the hd-256 kernel (kernels_attn256.hip)
 int attn_decode_path(int nh, int nkv, int hd, int nchunk);
+// fp8 (e4m3) KV cache, hd 128 (kernels_kv8.hip).  k8 / v8: u8 (nkv, max_seq,
+// 128) codes; ks / vs: f32 (nkv, max_seq) power-of-two row scales; kc / vc /
+// vtc: the bf16 scratch of one layer's size.
+// quant: rows [p0, p0+S) of every kv head, scratch -> codes + scales, and the
+// dequantized values back over the scratch rows; p0 = *pos when pos != null
+void launch_kv8_quant(u16* kc, u16* vc, u16* vtc, unsigned char* k8,
+                      unsigned char* v8, float* ks, float* vs, const int* pos,
+                      int p0, int S, int nkv, int max_seq, hipStream_t s);
+// dequant: rows [lo, p0) of the scratch (K, V, V^T) from the codes
+void launch_kv8_dequant(u16* kc, u16* vc, u16* vtc, const unsigned char* k8,
+                        const unsigned char* v8, const float* ks,
+                        const float* vs, int lo, int p0, int nkv, int max_seq,
+                        hipStream_t s);
+// q-heads per block of k_attn_decode_kv8 (4 when G % 4 == 0, 2 for G == 2,
+// else 1) and its grid_y = nh / group
+int attn_decode_kv8_group(int nh, int nkv);
+int attn_decode_kv8_grid_y(int nh, int nkv);
+// ws / cnt as launch_attn_decode (cnt: grid_y words); nchunk <= 64
+void launch_attn_decode_kv8(const u16* q, const unsigned char* k8,
+                            const unsigned char* v8, const float* ks,
+                            const float* vs, const int* pos, float* ws,
+                            u32* cnt, u16* out, int nh, int nkv, int max_seq,
+                            int nchunk, int window, hipStream_t s);
 // hd 256 (kernels_attn256.hip).  attn256_group: q-heads per block of
 // k_attn_decode_256, the largest of 4|3|2|1 dividing nh / nkv, capped by
 // CAKE_ATTN256_GB (read per call; default 1 = per head, the faster route).  Same ws / cnt contract as

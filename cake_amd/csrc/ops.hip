@@ -445,6 +445,162 @@ extern "C" int cake_hip_op_attn_decode_seq(
   return ob_down16(b, (u16*)dout, (size_t)nlaunch * Sq, out);
 }
 
+// ---- fp8 KV cache op entries (kernels_kv8.hip; hd 128) ---------------------
+static int kv8_geom_err(const char* who, int nkv, int max_seq) {
+  if (nkv <= 0) return set_err(5, "%s: nkv %d must be positive", who, nkv);
+  if (max_seq < 32 || max_seq % 32 != 0)
+    return set_err(5, "%s: max_seq %d must be a positive multiple of 32", who,
+                   max_seq);
+  return 0;
+}
+static int ob_down(OpBufs& b, const void* src, size_t bytes, void* dst) {
+  HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, b.s));
+  HIP_TRY(hipStreamSynchronize(b.s));
+  return 0;
+}
+
+extern "C" int cake_hip_op_kv8_quant(int S, int pos0, int decode, int nkv,
+                                     int max_seq, float* kc, float* vc,
+                                     float* vtc, uint8_t* k8, uint8_t* v8,
+                                     float* ks, float* vs, int device) {
+  const char* who = "op_kv8_quant";
+  int r = kv8_geom_err(who, nkv, max_seq);
+  if (r) return r;
+  if (S < 1 || pos0 < 0 || pos0 + S > max_seq)
+    return set_err(5, "%s: rows [%d,%d+%d) outside the cache (max_seq %d)",
+                   who, pos0, pos0, S, max_seq);
+  if (decode && S != 1)
+    return set_err(5, "%s: decode stores one row (S %d)", who, S);
+  OpBufs b;
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreate(&b.s));
+  const size_t rows = (size_t)nkv * max_seq, n = rows * 128;
+  u16 *dkc, *dvc, *dvtc;
+  void *dk8, *dv8, *dks, *dvs, *dpos;
+  if ((r = ob_up16(b, kc, n, &dkc))) return r;
+  if ((r = ob_up16(b, vc, n, &dvc))) return r;
+  if ((r = ob_up16(b, vtc, n, &dvtc))) return r;
+  if ((r = ob_upf32(b, k8, n, &dk8))) return r;
+  if ((r = ob_upf32(b, v8, n, &dv8))) return r;
+  if ((r = ob_upf32(b, ks, rows * 4, &dks))) return r;
+  if ((r = ob_upf32(b, vs, rows * 4, &dvs))) return r;
+  if ((r = ob_upf32(b, &pos0, sizeof(int), &dpos))) return r;
+  launch_kv8_quant(dkc, dvc, dvtc, (uint8_t*)dk8, (uint8_t*)dv8, (float*)dks,
+                   (float*)dvs, decode ? (const int*)dpos : nullptr,
+                   decode ? 0 : pos0, S, nkv, max_seq, b.s);
+  HIP_TRY(hipGetLastError());
+  if ((r = ob_down(b, dk8, n, k8))) return r;
+  if ((r = ob_down(b, dv8, n, v8))) return r;
+  if ((r = ob_down(b, dks, rows * 4, ks))) return r;
+  if ((r = ob_down(b, dvs, rows * 4, vs))) return r;
+  if ((r = ob_down16(b, dkc, n, kc))) return r;
+  if ((r = ob_down16(b, dvc, n, vc))) return r;
+  return ob_down16(b, dvtc, n, vtc);
+}
+
+extern "C" int cake_hip_op_kv8_dequant(int lo, int p0, int nkv, int max_seq,
+                                       const uint8_t* k8, const uint8_t* v8,
+                                       const float* ks, const float* vs,
+                                       float* kc, float* vc, float* vtc,
+                                       int device) {
+  const char* who = "op_kv8_dequant";
+  int r = kv8_geom_err(who, nkv, max_seq);
+  if (r) return r;
+  if (lo < 0 || p0 < 0 || p0 > max_seq)  // p0 <= lo: an empty range
+    return set_err(5, "%s: rows [%d,%d) outside the cache (max_seq %d)", who,
+                   lo, p0, max_seq);
+  OpBufs b;
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreate(&b.s));
+  const size_t rows = (size_t)nkv * max_seq, n = rows * 128;
+  u16 *dkc, *dvc, *dvtc;
+  void *dk8, *dv8, *dks, *dvs;
+  if ((r = ob_up16(b, kc, n, &dkc))) return r;
+  if ((r = ob_up16(b, vc, n, &dvc))) return r;
+  if ((r = ob_up16(b, vtc, n, &dvtc))) return r;
+  if ((r = ob_upf32(b, k8, n, &dk8))) return r;
+  if ((r = ob_upf32(b, v8, n, &dv8))) return r;
+  if ((r = ob_upf32(b, ks, rows * 4, &dks))) return r;
+  if ((r = ob_upf32(b, vs, rows * 4, &dvs))) return r;
+  launch_kv8_dequant(dkc, dvc, dvtc, (const uint8_t*)dk8, (const uint8_t*)dv8,
+                     (const float*)dks, (const float*)dvs, lo, p0, nkv,
+                     max_seq, b.s);
+  HIP_TRY(hipGetLastError());
+  if ((r = ob_down16(b, dkc, n, kc))) return r;
+  if ((r = ob_down16(b, dvc, n, vc))) return r;
+  return ob_down16(b, dvtc, n, vtc);
+}
+
+extern "C" int cake_hip_op_attn_decode_kv8(int nh, int nkv, int max_seq,
+                                           int pos, int window, int nchunk,
+                                           int repeats, const float* q,
+                                           const uint8_t* k8,
+                                           const uint8_t* v8, const float* ks,
+                                           const float* vs, float* out,
+                                           int device) {
+  const char* who = "op_attn_decode_kv8";
+  int r = attn_geom_err(who, nh, nkv, 128, max_seq);
+  if (r) return r;
+  if (pos < 0 || pos + 1 > max_seq)
+    return set_err(5, "%s: pos %d outside the cache (max_seq %d)", who, pos,
+                   max_seq);
+  if (window < 0) return set_err(5, "%s: window %d < 0", who, window);
+  if (nchunk < 1 || nchunk > 64)
+    return set_err(5, "%s: nchunk %d outside [1,64]", who, nchunk);
+  if (repeats < 1 || repeats > 16)
+    return set_err(5, "%s: repeats %d outside [1,16]", who, repeats);
+  OpBufs b;
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipStreamCreate(&b.s));
+  const int Sq = nh * 128;
+  const size_t rows = (size_t)nkv * max_seq, n = rows * 128;
+  u16* dq;
+  void *dk8, *dv8, *dks, *dvs, *dout, *dws, *dcnt, *dpos;
+  if ((r = ob_up16(b, q, Sq, &dq))) return r;
+  if ((r = ob_upf32(b, k8, n, &dk8))) return r;
+  if ((r = ob_upf32(b, v8, n, &dv8))) return r;
+  if ((r = ob_upf32(b, ks, rows * 4, &dks))) return r;
+  if ((r = ob_upf32(b, vs, rows * 4, &dvs))) return r;
+  if ((r = ob_alloc(b, &dout, (size_t)repeats * Sq * 2))) return r;
+  if ((r = ob_alloc(b, &dws, (size_t)nh * 64 * 132 * 4))) return r;
+  if ((r = ob_alloc(b, &dcnt, (size_t)nh * 4))) return r;
+  if ((r = ob_upf32(b, &pos, sizeof(int), &dpos))) return r;
+  HIP_TRY(hipMemsetAsync(dout, 0, (size_t)repeats * Sq * 2, b.s));
+  // counters zeroed once, as in cake_hip_op_attn_decode
+  HIP_TRY(hipMemsetAsync(dcnt, 0, (size_t)nh * 4, b.s));
+  for (int i = 0; i < repeats; ++i)
+    launch_attn_decode_kv8(dq, (const uint8_t*)dk8, (const uint8_t*)dv8,
+                           (const float*)dks, (const float*)dvs,
+                           (const int*)dpos, (float*)dws, (u32*)dcnt,
+                           (u16*)dout + (size_t)i * Sq, nh, nkv, max_seq,
+                           nchunk, window, b.s);
+  HIP_TRY(hipGetLastError());
+  return ob_down16(b, (u16*)dout, (size_t)repeats * Sq, out);
+}
+
+// Host only: the KV-cache plan of engine create for this config and max_seq:
+// out = {format (0 bf16, 1 fp8_e4m3), KV bytes per layer, shared scratch
+// bytes, q-heads per decode-attention block, its grid_y}.
+extern "C" int cake_hip_kv_dispatch(const char* config_json, int max_seq,
+                                    int64_t out[5]) {
+  ModelConfig c;
+  int r = parse_config(config_json, &c);
+  if (r) return r;
+  if ((r = kv8_config_err(c))) return r;
+  if (c.nkv <= 0 || c.nh % c.nkv != 0)
+    return set_err(5, "kv_dispatch: nh %d must be a positive multiple of nkv "
+                   "%d", c.nh, c.nkv);
+  if (max_seq <= 0) max_seq = c.max_pos;
+  max_seq = (max_seq + 31) & ~31;  // as engine create
+  out[0] = c.kv8 ? 1 : 0;
+  out[1] = (int64_t)kv_layer_bytes(c, max_seq);
+  out[2] = (int64_t)kv_scratch_bytes(c, max_seq);
+  out[3] = c.kv8 ? attn_decode_kv8_group(c.nh, c.nkv)
+                 : cake_hip_attn_decode_group(c.nh, c.nkv, c.hd());
+  out[4] = c.kv8 ? attn_decode_kv8_grid_y(c.nh, c.nkv) : c.nh / out[3];
+  return 0;
+}
+
 // ---- linear op entries (GEMV / fp8 / GEMM) ---------------------------------
 // Same conventions as the attention entries.  Every output buffer carries
 // CAKE_HIP_OP_GUARD extra elements past its end and is pre-filled with

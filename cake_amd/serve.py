@@ -295,13 +295,17 @@ def main():
     ap.add_argument("--port", type=int, default=8000)
     ap.add_argument("--host", default="127.0.0.1")
     ap.add_argument("--max-seq", type=int, default=4096)
+    ap.add_argument("--kv-dtype", default=None,
+                    choices=("bf16", "fp8_e4m3"),
+                    help="KV-cache format; fp8_e4m3 (head_dim 128 models) "
+                    "stores e4m3 codes with a power-of-two scale per row")
     args = ap.parse_args()
 
     import cake_amd
     from cake_amd.configs import find_model
     cfg = find_model(args.model)
     eng = cake_amd.Engine(json.dumps(cfg), max_seq=args.max_seq,
-                          max_batch_tokens=2048)
+                          max_batch_tokens=2048, kv_dtype=args.kv_dtype)
     if args.safetensors:
         eng.load_safetensors(args.safetensors)
     else:

@@ -268,6 +268,42 @@ int cake_hip_op_attn_decode_seq(int nh, int nkv, int hd, int max_seq, int pos,
                                 const float *vc, float *out,
                                 uint32_t *cnt_out, int device);
 
+/* fp8 (e4m3) KV cache, head_dim 128 (test-only op entries).  k8 / v8: u8
+ * (nkv, max_seq, 128) OCP e4m3 codes; ks / vs: f32 (nkv, max_seq), one scale
+ * 2^k per row, k the smallest integer with amax(row) * 2^-k <= 448 (an
+ * all-zero row: 1); code = round-to-nearest-even e4m3 of x * 2^-k.  kc / vc
+ * (nkv, max_seq, 128) and vtc (nkv, 128, max_seq) are the bf16 scratch images,
+ * crossing as f32.
+ * quant: reads rows [pos0, pos0+S) of kc and vc, writes their codes and
+ * scales, and writes code * scale back over those rows of kc, vc and vtc.
+ * All seven buffers are in-out; rows outside the range keep what the caller
+ * put there.  decode != 0 (S == 1): the position is read from device memory,
+ * as the decode graph does. */
+int cake_hip_op_kv8_quant(int S, int pos0, int decode, int nkv, int max_seq,
+                          float *kc, float *vc, float *vtc, uint8_t *k8,
+                          uint8_t *v8, float *ks, float *vs, int device);
+/* dequant: rows [lo, p0) of kc, vc and vtc (in-out) = code * scale. */
+int cake_hip_op_kv8_dequant(int lo, int p0, int nkv, int max_seq,
+                            const uint8_t *k8, const uint8_t *v8,
+                            const float *ks, const float *vs, float *kc,
+                            float *vc, float *vtc, int device);
+/* cake_hip_op_attn_decode over the codes and scales as given (hd 128):
+ * k_attn_decode_kv8, GB = 4 when nh / nkv is a multiple of 4, 2 for 2, else
+ * 1 with one block row per q head. */
+int cake_hip_op_attn_decode_kv8(int nh, int nkv, int max_seq, int pos,
+                                int window, int nchunk, int repeats,
+                                const float *q, const uint8_t *k8,
+                                const uint8_t *v8, const float *ks,
+                                const float *vs, float *out, int device);
+/* Host only: the KV-cache plan of engine create.  The top-level config key
+ * kv_cache_dtype selects the format: "bf16" (the default) or "fp8_e4m3"
+ * (head_dim 128 only; anything else is error 5).  out = {format (0 bf16, 1
+ * fp8_e4m3), KV bytes per layer, bytes of the engine-wide bf16 scratch an fp8
+ * cache prefills through (0 for bf16), q-heads per block of the decode
+ * attention kernel, its grid_y}.  max_seq <= 0 = max_position_embeddings;
+ * rounded up to a multiple of 32 as engine create does. */
+int cake_hip_kv_dispatch(const char *config_json, int max_seq, int64_t out[5]);
+
 /* Linear-layer op entries (test-only): GEMV, fp8 GEMV, gate-up, fused
  * qkv-rope, prefill GEMM, fp8 dequant.  Conventions of the attention entries
  * (private buffers of exact size, private stream, arguments validated before

@@ -34,6 +34,10 @@ def main():
     ap.add_argument("--steps", type=int, default=256)
     ap.add_argument("--prompt-len", type=int, default=128)
     ap.add_argument("--max-seq", type=int, default=4096)
+    ap.add_argument("--kv-dtype", default=None,
+                    choices=("bf16", "fp8_e4m3"),
+                    help="KV-cache format; fp8_e4m3 (head_dim 128 models) "
+                    "stores e4m3 codes with a power-of-two scale per row")
     ap.add_argument("--stats", action="store_true")
     ap.add_argument("--stats-steps", type=int, default=8)
     ap.add_argument("--prefill-len", type=int, default=0)
@@ -44,7 +48,7 @@ def main():
     cfg = find_model(args.model)
     flags = cake_amd.HAS_EMBED | cake_amd.HAS_HEAD | cake_amd.USE_GRAPH
     eng = cake_amd.Engine(json.dumps(cfg), flags=flags, max_seq=args.max_seq,
-                          max_batch_tokens=2048)
+                          max_batch_tokens=2048, kv_dtype=args.kv_dtype)
     try:
         eng.init_random(seed=SEED, scale=0.02)
         rng = np.random.default_rng(SEED)
@@ -89,7 +93,8 @@ def main():
             # eager, per-kernel hipEvent timing
             e2 = cake_amd.Engine(json.dumps(cfg),
                                  flags=cake_amd.HAS_EMBED | cake_amd.HAS_HEAD,
-                                 max_seq=args.max_seq, max_batch_tokens=2048)
+                                 max_seq=args.max_seq, max_batch_tokens=2048,
+                                 kv_dtype=args.kv_dtype)
             try:
                 e2.init_random(seed=SEED, scale=0.02)
                 e2.prefill(prompt)
