@@ -453,7 +453,9 @@ def attn_decode_path(nh, nkv, hd, nchunk):
     """The decode-attention kernel the product launches for this geometry and
     chunk count (host only): 0 per-head, 1 grouped, 2 short-context (the
     default at nchunk 4).  The library reads CAKE_ATTN_SHORT on every call:
-    0 = never the short kernel, 2 = also at nchunk 8.  hd 256: 3."""
+    0 = never the short kernel, 2 = also at nchunk 8.  hd 256: 3.  With
+    CAKE_ATTN_MQ=1 (read on every call) hd 64 | 128 with at most 16 q-heads
+    per kv head: 4, the grouped MFMA kernel."""
     return _lib.cake_hip_attn_decode_path(nh, nkv, hd, nchunk)
 
 
@@ -461,7 +463,8 @@ def attn_decode_group(nh, nkv, hd):
     """q-heads per block of the decode-attention kernel at this geometry
     (host only).  hd 256: the largest of 4, 3, 2, 1 dividing nh / nkv, capped
     by CAKE_ATTN256_GB, which the library reads on every call (default 1: the
-    per-head route measured faster; 2..4 opt in to grouping)."""
+    per-head route measured faster; 2..4 opt in to grouping).  Under
+    CAKE_ATTN_MQ=1 (decode path 4): nh / nkv."""
     return _lib.cake_hip_attn_decode_group(nh, nkv, hd)
 
 
@@ -1038,14 +1041,21 @@ def comm_id() -> bytes:
 # ---------------------------------------------------------------------------
 class Engine:
     def __init__(self, config, layer_lo=0, layer_hi=None, flags=None,
-                 max_seq=0, max_batch_tokens=0, device=0, kv_dtype=None):
+                 max_seq=0, max_batch_tokens=0, device=0, kv_dtype=None,
+                 decode_attention=None):
         """kv_dtype: None = what the config says (kv_cache_dtype, default
-        "bf16"); "bf16" | "fp8_e4m3" overrides it."""
+        "bf16"); "bf16" | "fp8_e4m3" overrides it.  decode_attention: None =
+        what the config says (decode_attention, default "auto"); "auto" |
+        "mfma" (the grouped MFMA decode kernel: head_dim 64 | 128, at most 16
+        q-heads per kv head, bf16 cache) overrides it."""
         if isinstance(config, dict):
             config = json.dumps(config)
         if kv_dtype is not None:
             config = json.dumps({**json.loads(config),
                                  "kv_cache_dtype": kv_dtype})
+        if decode_attention is not None:
+            config = json.dumps({**json.loads(config),
+                                 "decode_attention": decode_attention})
         cfg = json.loads(config)
         if cfg.get("model_type") == "gemma3":
             # the multimodal form: the text model's fields, HF's defaults

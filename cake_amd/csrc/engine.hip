@@ -368,6 +368,15 @@ int parse_config(const char* json, ModelConfig* c) {
                        p->kind == minijson::Value::Str ? p->str.c_str() : "?");
       c->kv8 = p->str == "fp8_e4m3";
     }
+  if (auto p = root->get("decode_attention"))
+    if (!p->is_null()) {
+      if (p->kind != minijson::Value::Str ||
+          (p->str != "auto" && p->str != "mfma"))
+        return set_err(5, "config.json: decode_attention %s is not supported "
+                          "(auto or mfma)",
+                       p->kind == minijson::Value::Str ? p->str.c_str() : "?");
+      c->attn_mq = p->str == "mfma";
+    }
   if (c->fused_ckpt && c->fp8)
     return set_err(5, "config.json: quant_method fp8 with model_type phi3 is "
                       "not supported");
@@ -488,6 +497,19 @@ int kv8_config_err(const ModelConfig& c) {
   if (c.kv8 && c.hd() != 128)
     return set_err(5, "config.json: kv_cache_dtype fp8_e4m3 needs head_dim "
                       "128 (got head_dim %d)", c.hd());
+  return 0;
+}
+// decode_attention "mfma" (host only; engine create and cake_hip_kv_dispatch)
+int attn_mq_config_err(const ModelConfig& c) {
+  if (!c.attn_mq) return 0;
+  if (c.kv8)
+    return set_err(5, "config.json: decode_attention mfma reads the bf16 KV "
+                      "cache (got kv_cache_dtype fp8_e4m3)");
+  if (!attn_decode_mq_on(c.nh, c.nkv, c.hd(), 1))
+    return set_err(5, "config.json: decode_attention mfma needs head_dim 64 "
+                      "or 128 and at most 16 q-heads per kv head (got "
+                      "head_dim %d, %d q-heads, %d kv heads)", c.hd(), c.nh,
+                   c.nkv);
   return 0;
 }
 size_t kv_layer_bytes(const ModelConfig& c, int max_seq) {
@@ -877,7 +899,8 @@ static void enqueue_layer_decode(cake_engine* e, LayerDev& l,
                  4.0 * (e->host_pos + 1) * Sq);
     launch_attn_decode(e->qkv, l.kc, l.vc, e->dev_pos, e->attn_ws,
                        e->attn_cnt, e->attn_out, c.nh, c.nkv, hd, e->max_seq,
-                       e->nchunk, c.win_for(l.idx), e->stream);
+                       e->nchunk, c.win_for(l.idx), e->stream,
+                       c.attn_mq ? 1 : -1);
   }
   if (c.gemma3) {  // sandwich norms: o and down go through their post-norm
     enqueue_post_proj(e, l.o, "gemv_o", e->attn_out, l.post1);
@@ -1118,6 +1141,7 @@ static int engine_build(const char* config_json, int layer_lo, int layer_hi,
   if (c.w4 && (r = w4_config_err(c))) return r;
   if (c.mx4 && (r = mx4_config_err(c))) return r;
   if ((r = kv8_config_err(c))) return r;
+  if ((r = attn_mq_config_err(c))) return r;
   if (max_seq <= 0) max_seq = c.max_pos;
   max_seq = (max_seq + 31) & ~31;  // MFMA prefill reads whole 32-pos tiles
   if (max_batch_tokens <= 0) max_batch_tokens = 2048;
@@ -1566,7 +1590,13 @@ extern "C" int cake_hip_decode(cake_engine* e, int steps,
   // env knob kept for experiments
   static const int nc1_tiles =
       getenv("CAKE_NC1_TILES") ? atoi(getenv("CAKE_NC1_TILES")) : 0;
-  const int gy = attn_decode_grid_y(e->c.nh, e->c.nkv, e->c.hd());
+  // the grouped MFMA kernel (decode_attention "mfma" or CAKE_ATTN_MQ) has
+  // nkv blocks per chunk and follows the grouped curve; an fp8 KV cache
+  // never runs it, whatever the environment says
+  const bool mq = !e->c.kv8 && attn_decode_mq_on(e->c.nh, e->c.nkv, e->c.hd(),
+                                                 e->c.attn_mq ? 1 : -1);
+  const int gy =
+      mq ? e->c.nkv : attn_decode_grid_y(e->c.nh, e->c.nkv, e->c.hd());
   auto want_nchunk = [gy](int pos) {
     if (gy > 0) {
       const int span_tiles = (pos + 64) / 64;

@@ -83,6 +83,10 @@ struct ModelConfig {
   // power-of-two scale per (layer, kv head, position) row (kernels_kv8.hip);
   // absent or "bf16" = the bf16 cache.  hd 128 only (kv8_config_err).
   bool kv8 = false;
+  // decode_attention "mfma": decode attention runs the grouped MFMA kernel
+  // (kernels_attn_mq.hip; launch_attn_decode's mq = 1); absent or "auto" =
+  // the default routing.  hd 64 | 128, G <= 16, bf16 cache (attn_mq_config_err).
+  bool attn_mq = false;
   // llama3 rope scaling (config.rs:50-65)
   bool rope_llama3 = false;
   float rs_factor = 1, rs_low = 1, rs_high = 4;
@@ -117,6 +121,8 @@ int mx4_dim_err(const char* name, int N, int K);
 int mx4_config_err(const ModelConfig& c);
 // fp8 KV cache: head_dim 128 only
 int kv8_config_err(const ModelConfig& c);
+// decode_attention "mfma": head_dim 64 | 128, nh / nkv <= 16, bf16 KV cache
+int attn_mq_config_err(const ModelConfig& c);
 // bytes of one layer's KV cache in the config's format, and of the engine-wide
 // bf16 scratch an fp8 cache attends through in prefill (0 for bf16)
 size_t kv_layer_bytes(const ModelConfig& c, int max_seq);

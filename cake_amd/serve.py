@@ -299,13 +299,19 @@ def main():
                     choices=("bf16", "fp8_e4m3"),
                     help="KV-cache format; fp8_e4m3 (head_dim 128 models) "
                     "stores e4m3 codes with a power-of-two scale per row")
+    ap.add_argument("--decode-attention", default=None,
+                    choices=("auto", "mfma"),
+                    help="decode-attention kernel; mfma (head_dim 64 | 128, at "
+                    "most 16 q-heads per kv head, bf16 cache) reads K/V once "
+                    "per kv head through the grouped MFMA kernel")
     args = ap.parse_args()
 
     import cake_amd
     from cake_amd.configs import find_model
     cfg = find_model(args.model)
     eng = cake_amd.Engine(json.dumps(cfg), max_seq=args.max_seq,
-                          max_batch_tokens=2048, kv_dtype=args.kv_dtype)
+                          max_batch_tokens=2048, kv_dtype=args.kv_dtype,
+                          decode_attention=args.decode_attention)
     if args.safetensors:
         eng.load_safetensors(args.safetensors)
     else:

@@ -445,6 +445,11 @@ def main():
                     choices=("bf16", "fp8_e4m3"),
                     help="KV-cache format; fp8_e4m3 (head_dim 128 models) "
                     "stores e4m3 codes with a power-of-two scale per row")
+    ap.add_argument("--decode-attention", default=None,
+                    choices=("auto", "mfma"),
+                    help="decode-attention kernel; mfma (head_dim 64 | 128, at "
+                    "most 16 q-heads per kv head, bf16 cache) reads K/V once "
+                    "per kv head through the grouped MFMA kernel")
     args = ap.parse_args()
 
     import cake_amd
@@ -457,7 +462,8 @@ def main():
         lo, hi = 0, cfg["num_hidden_layers"]
     eng = cake_amd.Engine(json.dumps(cfg), layer_lo=lo, layer_hi=hi, flags=0,
                           max_seq=args.max_seq, max_batch_tokens=2048,
-                          kv_dtype=args.kv_dtype)
+                          kv_dtype=args.kv_dtype,
+                          decode_attention=args.decode_attention)
     if args.safetensors:
         eng.load_safetensors(args.safetensors)
     else:

@@ -301,7 +301,15 @@ int cake_hip_op_attn_decode_kv8(int nh, int nkv, int max_seq, int pos,
  * fp8_e4m3), KV bytes per layer, bytes of the engine-wide bf16 scratch an fp8
  * cache prefills through (0 for bf16), q-heads per block of the decode
  * attention kernel, its grid_y}.  max_seq <= 0 = max_position_embeddings;
- * rounded up to a multiple of 32 as engine create does. */
+ * rounded up to a multiple of 32 as engine create does.
+ * The top-level config key decode_attention selects the decode-attention
+ * kernel: "auto" (the default routing) or "mfma", the grouped MFMA kernel that
+ * serves all nh / nkv q-heads of a kv head from one K/V read (out[3] = nh /
+ * nkv, out[4] = nkv).  "mfma" needs head_dim 64 or 128, nh / nkv <= 16 and the
+ * bf16 cache; anything else, and any other value, is error 5 here and at
+ * engine create, with decode_attention named in the message.  The environment
+ * variable CAKE_ATTN_MQ=1 (read per launch) routes eligible shapes there
+ * without the key; cake_hip_attn_decode_path then answers 4. */
 int cake_hip_kv_dispatch(const char *config_json, int max_seq, int64_t out[5]);
 
 /* Linear-layer op entries (test-only): GEMV, fp8 GEMV, gate-up, fused

@@ -38,6 +38,11 @@ def main():
                     choices=("bf16", "fp8_e4m3"),
                     help="KV-cache format; fp8_e4m3 (head_dim 128 models) "
                     "stores e4m3 codes with a power-of-two scale per row")
+    ap.add_argument("--decode-attention", default=None,
+                    choices=("auto", "mfma"),
+                    help="decode-attention kernel; mfma (head_dim 64 | 128, at "
+                    "most 16 q-heads per kv head, bf16 cache) reads K/V once "
+                    "per kv head through the grouped MFMA kernel")
     ap.add_argument("--stats", action="store_true")
     ap.add_argument("--stats-steps", type=int, default=8)
     ap.add_argument("--prefill-len", type=int, default=0)
@@ -48,7 +53,8 @@ def main():
     cfg = find_model(args.model)
     flags = cake_amd.HAS_EMBED | cake_amd.HAS_HEAD | cake_amd.USE_GRAPH
     eng = cake_amd.Engine(json.dumps(cfg), flags=flags, max_seq=args.max_seq,
-                          max_batch_tokens=2048, kv_dtype=args.kv_dtype)
+                          max_batch_tokens=2048, kv_dtype=args.kv_dtype,
+                          decode_attention=args.decode_attention)
     try:
         eng.init_random(seed=SEED, scale=0.02)
         rng = np.random.default_rng(SEED)
@@ -94,7 +100,8 @@ def main():
             e2 = cake_amd.Engine(json.dumps(cfg),
                                  flags=cake_amd.HAS_EMBED | cake_amd.HAS_HEAD,
                                  max_seq=args.max_seq, max_batch_tokens=2048,
-                                 kv_dtype=args.kv_dtype)
+                                 kv_dtype=args.kv_dtype,
+                                 decode_attention=args.decode_attention)
             try:
                 e2.init_random(seed=SEED, scale=0.02)
                 e2.prefill(prompt)
