@@ -135,6 +135,8 @@ def _load_lib():
         [c]
     lib.cake_hip_op_attn_decode_kv8.argtypes = [c] * 7 + [fp, u8p, u8p] + \
         [fp] * 3 + [c]
+    lib.cake_hip_op_attn_decode_kv8_mq.argtypes = \
+        lib.cake_hip_op_attn_decode_kv8.argtypes
     lib.cake_hip_kv_dispatch.argtypes = [cp, c,
                                          ctypes.POINTER(ctypes.c_int64)]
     lib.cake_hip_sync.argtypes = [p]
@@ -387,10 +389,11 @@ def op_kv8_dequant(k8, v8, ks, vs, kc, vc, vtc, lo, p0, device=0):
 
 
 def op_attn_decode_kv8(q, k8, v8, ks, vs, pos, window=0, nchunk=8, repeats=1,
-                       device=0):
+                       device=0, mq=False):
     """op_attn_decode over an fp8 cache: q (nh, 128), codes k8 / v8 (nkv,
     max_seq, 128) u8 and row scales ks / vs (nkv, max_seq), read as given.
-    Returns (repeats, nh*128)."""
+    mq: the grouped MFMA kernel over the codes (decode_attention "mfma_kv8";
+    at most 16 q-heads per kv head).  Returns (repeats, nh*128)."""
     q = np.ascontiguousarray(q, dtype=np.float32)
     nh = q.shape[0]
     k8 = np.ascontiguousarray(k8, dtype=np.uint8)
@@ -401,7 +404,9 @@ def op_attn_decode_kv8(q, k8, v8, ks, vs, pos, window=0, nchunk=8, repeats=1,
     _s, ksp = _f32_shaped(ks, (nkv, max_seq), "ks")
     _t, vsp = _f32_shaped(vs, (nkv, max_seq), "vs")
     out = np.empty((max(repeats, 0), nh * 128), dtype=np.float32)
-    _check(_lib.cake_hip_op_attn_decode_kv8(
+    entry = (_lib.cake_hip_op_attn_decode_kv8_mq if mq
+             else _lib.cake_hip_op_attn_decode_kv8)
+    _check(entry(
         nh, nkv, max_seq, pos, window, nchunk, repeats, qp, k8p, v8p, ksp,
         vsp, out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), device))
     return out
@@ -1047,7 +1052,8 @@ class Engine:
         "bf16"); "bf16" | "fp8_e4m3" overrides it.  decode_attention: None =
         what the config says (decode_attention, default "auto"); "auto" |
         "mfma" (the grouped MFMA decode kernel: head_dim 64 | 128, at most 16
-        q-heads per kv head, bf16 cache) overrides it."""
+        q-heads per kv head, bf16 cache) | "mfma_kv8" (the same over an
+        fp8_e4m3 cache) overrides it."""
         if isinstance(config, dict):
             config = json.dumps(config)
         if kv_dtype is not None:

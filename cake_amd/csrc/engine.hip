@@ -371,11 +371,12 @@ int parse_config(const char* json, ModelConfig* c) {
   if (auto p = root->get("decode_attention"))
     if (!p->is_null()) {
       if (p->kind != minijson::Value::Str ||
-          (p->str != "auto" && p->str != "mfma"))
+          (p->str != "auto" && p->str != "mfma" && p->str != "mfma_kv8"))
         return set_err(5, "config.json: decode_attention %s is not supported "
-                          "(auto or mfma)",
+                          "(auto, mfma or mfma_kv8)",
                        p->kind == minijson::Value::Str ? p->str.c_str() : "?");
       c->attn_mq = p->str == "mfma";
+      c->attn_kv8_mq = p->str == "mfma_kv8";
     }
   if (c->fused_ckpt && c->fp8)
     return set_err(5, "config.json: quant_method fp8 with model_type phi3 is "
@@ -499,12 +500,25 @@ int kv8_config_err(const ModelConfig& c) {
                       "128 (got head_dim %d)", c.hd());
   return 0;
 }
-// decode_attention "mfma" (host only; engine create and cake_hip_kv_dispatch)
+// decode_attention "mfma" and "mfma_kv8" (host only; engine create and
+// cake_hip_kv_dispatch)
 int attn_mq_config_err(const ModelConfig& c) {
+  if (c.attn_kv8_mq) {
+    if (!c.kv8)
+      return set_err(5, "config.json: decode_attention mfma_kv8 reads the "
+                        "fp8_e4m3 KV cache (got kv_cache_dtype bf16; the bf16 "
+                        "cache takes decode_attention mfma)");
+    if (!attn_decode_kv8_mq_on(c.nh, c.nkv))
+      return set_err(5, "config.json: decode_attention mfma_kv8 needs at most "
+                        "16 q-heads per kv head (got %d q-heads, %d kv heads)",
+                     c.nh, c.nkv);
+    return 0;
+  }
   if (!c.attn_mq) return 0;
   if (c.kv8)
     return set_err(5, "config.json: decode_attention mfma reads the bf16 KV "
-                      "cache (got kv_cache_dtype fp8_e4m3)");
+                      "cache (got kv_cache_dtype fp8_e4m3, which takes "
+                      "decode_attention mfma_kv8)");
   if (!attn_decode_mq_on(c.nh, c.nkv, c.hd(), 1))
     return set_err(5, "config.json: decode_attention mfma needs head_dim 64 "
                       "or 128 and at most 16 q-heads per kv head (got "
@@ -890,9 +904,10 @@ static void enqueue_layer_decode(cake_engine* e, LayerDev& l,
     const double n = e->host_pos + 1;
     StatScope ss(e, "attn_decode_kv8",
                  2.0 * n * (c.skv() + c.nkv * 4) + Sq * 2 * 2, 4.0 * n * Sq);
-    launch_attn_decode_kv8(e->qkv, l.k8, l.v8, l.ks, l.vs, e->dev_pos,
-                           e->attn_ws, e->attn_cnt, e->attn_out, c.nh, c.nkv,
-                           e->max_seq, e->nchunk, c.win_for(l.idx), e->stream);
+    (c.attn_kv8_mq ? launch_attn_decode_kv8_mq : launch_attn_decode_kv8)(
+        e->qkv, l.k8, l.v8, l.ks, l.vs, e->dev_pos, e->attn_ws, e->attn_cnt,
+        e->attn_out, c.nh, c.nkv, e->max_seq, e->nchunk, c.win_for(l.idx),
+        e->stream);
   } else {  // decode attention over the cache (single launch, split-KV combine)
     double kvbytes = 2.0 * (e->host_pos + 1) * c.skv() * 2;
     StatScope ss(e, "attn_decode", kvbytes + Sq * 2 * 2,
@@ -1592,9 +1607,11 @@ extern "C" int cake_hip_decode(cake_engine* e, int steps,
       getenv("CAKE_NC1_TILES") ? atoi(getenv("CAKE_NC1_TILES")) : 0;
   // the grouped MFMA kernel (decode_attention "mfma" or CAKE_ATTN_MQ) has
   // nkv blocks per chunk and follows the grouped curve; an fp8 KV cache
-  // never runs it, whatever the environment says
-  const bool mq = !e->c.kv8 && attn_decode_mq_on(e->c.nh, e->c.nkv, e->c.hd(),
-                                                 e->c.attn_mq ? 1 : -1);
+  // never runs it, whatever the environment says: there only
+  // decode_attention "mfma_kv8" selects the grouped MFMA kernel over the codes
+  const bool mq = e->c.kv8 ? e->c.attn_kv8_mq
+                           : attn_decode_mq_on(e->c.nh, e->c.nkv, e->c.hd(),
+                                               e->c.attn_mq ? 1 : -1);
   const int gy =
       mq ? e->c.nkv : attn_decode_grid_y(e->c.nh, e->c.nkv, e->c.hd());
   auto want_nchunk = [gy](int pos) {

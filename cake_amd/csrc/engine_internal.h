@@ -87,6 +87,10 @@ struct ModelConfig {
   // (kernels_attn_mq.hip; launch_attn_decode's mq = 1); absent or "auto" =
   // the default routing.  hd 64 | 128, G <= 16, bf16 cache (attn_mq_config_err).
   bool attn_mq = false;
+  // decode_attention "mfma_kv8": decode attention over an fp8 cache runs the
+  // grouped MFMA kernel over the codes (kernels_kv8_mq.hip).  fp8_e4m3 cache
+  // (hence hd 128), G <= 16 (attn_mq_config_err).
+  bool attn_kv8_mq = false;
   // llama3 rope scaling (config.rs:50-65)
   bool rope_llama3 = false;
   float rs_factor = 1, rs_low = 1, rs_high = 4;
@@ -121,7 +125,8 @@ int mx4_dim_err(const char* name, int N, int K);
 int mx4_config_err(const ModelConfig& c);
 // fp8 KV cache: head_dim 128 only
 int kv8_config_err(const ModelConfig& c);
-// decode_attention "mfma": head_dim 64 | 128, nh / nkv <= 16, bf16 KV cache
+// decode_attention "mfma": head_dim 64 | 128, nh / nkv <= 16, bf16 KV cache;
+// "mfma_kv8": fp8_e4m3 KV cache, nh / nkv <= 16
 int attn_mq_config_err(const ModelConfig& c);
 // bytes of one layer's KV cache in the config's format, and of the engine-wide
 // bf16 scratch an fp8 cache attends through in prefill (0 for bf16)

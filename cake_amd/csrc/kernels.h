@@ -214,6 +214,20 @@ void launch_attn_decode_kv8(const u16* q, const unsigned char* k8,
                             const float* vs, const int* pos, float* ws,
                             u32* cnt, u16* out, int nh, int nkv, int max_seq,
                             int nchunk, int window, hipStream_t s);
+// Grouped MFMA decode attention over the fp8 cache, k_attn_decode_kv8_mq
+// (kernels_kv8_mq.hip; config decode_attention "mfma_kv8"): grid (nchunk,
+// nkv), all G = nh / nkv q-heads of a kv head in one block, codes read and
+// converted once per kv head.  attn_decode_kv8_mq_on: nh % nkv == 0, G <= 16.
+// ws as launch_attn_decode; cnt: nkv words, modulo-nchunk election, the
+// elected block stores 0 to its word.  The launcher checks 1 <= nchunk <= 64
+// and the shape itself: outside them it launches nothing and says so on stderr.
+bool attn_decode_kv8_mq_on(int nh, int nkv);
+void launch_attn_decode_kv8_mq(const u16* q, const unsigned char* k8,
+                               const unsigned char* v8, const float* ks,
+                               const float* vs, const int* pos, float* ws,
+                               u32* cnt, u16* out, int nh, int nkv,
+                               int max_seq, int nchunk, int window,
+                               hipStream_t s);
 // hd 256 (kernels_attn256.hip).  attn256_group: q-heads per block of
 // k_attn_decode_256, the largest of 4|3|2|1 dividing nh / nkv, capped by
 // CAKE_ATTN256_GB (read per call; default 1 = per head, the faster route).  Same ws / cnt contract as

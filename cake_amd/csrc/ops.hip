@@ -533,16 +533,17 @@ extern "C" int cake_hip_op_kv8_dequant(int lo, int p0, int nkv, int max_seq,
   return ob_down16(b, dvtc, n, vtc);
 }
 
-extern "C" int cake_hip_op_attn_decode_kv8(int nh, int nkv, int max_seq,
-                                           int pos, int window, int nchunk,
-                                           int repeats, const float* q,
-                                           const uint8_t* k8,
-                                           const uint8_t* v8, const float* ks,
-                                           const float* vs, float* out,
-                                           int device) {
-  const char* who = "op_attn_decode_kv8";
+// mq: the grouped MFMA kernel over the codes (kernels_kv8_mq.hip)
+static int op_attn_decode_kv8(const char* who, bool mq, int nh, int nkv,
+                              int max_seq, int pos, int window, int nchunk,
+                              int repeats, const float* q, const uint8_t* k8,
+                              const uint8_t* v8, const float* ks,
+                              const float* vs, float* out, int device) {
   int r = attn_geom_err(who, nh, nkv, 128, max_seq);
   if (r) return r;
+  if (mq && !attn_decode_kv8_mq_on(nh, nkv))
+    return set_err(5, "%s: nh %d / nkv %d above 16 q-heads per kv head", who,
+                   nh, nkv);
   if (pos < 0 || pos + 1 > max_seq)
     return set_err(5, "%s: pos %d outside the cache (max_seq %d)", who, pos,
                    max_seq);
@@ -571,13 +572,34 @@ extern "C" int cake_hip_op_attn_decode_kv8(int nh, int nkv, int max_seq,
   // counters zeroed once, as in cake_hip_op_attn_decode
   HIP_TRY(hipMemsetAsync(dcnt, 0, (size_t)nh * 4, b.s));
   for (int i = 0; i < repeats; ++i)
-    launch_attn_decode_kv8(dq, (const uint8_t*)dk8, (const uint8_t*)dv8,
-                           (const float*)dks, (const float*)dvs,
-                           (const int*)dpos, (float*)dws, (u32*)dcnt,
-                           (u16*)dout + (size_t)i * Sq, nh, nkv, max_seq,
-                           nchunk, window, b.s);
+    (mq ? launch_attn_decode_kv8_mq : launch_attn_decode_kv8)(
+        dq, (const uint8_t*)dk8, (const uint8_t*)dv8, (const float*)dks,
+        (const float*)dvs, (const int*)dpos, (float*)dws, (u32*)dcnt,
+        (u16*)dout + (size_t)i * Sq, nh, nkv, max_seq, nchunk, window, b.s);
   HIP_TRY(hipGetLastError());
   return ob_down16(b, (u16*)dout, (size_t)repeats * Sq, out);
+}
+extern "C" int cake_hip_op_attn_decode_kv8(int nh, int nkv, int max_seq,
+                                           int pos, int window, int nchunk,
+                                           int repeats, const float* q,
+                                           const uint8_t* k8,
+                                           const uint8_t* v8, const float* ks,
+                                           const float* vs, float* out,
+                                           int device) {
+  return op_attn_decode_kv8("op_attn_decode_kv8", false, nh, nkv, max_seq, pos,
+                            window, nchunk, repeats, q, k8, v8, ks, vs, out,
+                            device);
+}
+extern "C" int cake_hip_op_attn_decode_kv8_mq(int nh, int nkv, int max_seq,
+                                              int pos, int window, int nchunk,
+                                              int repeats, const float* q,
+                                              const uint8_t* k8,
+                                              const uint8_t* v8,
+                                              const float* ks, const float* vs,
+                                              float* out, int device) {
+  return op_attn_decode_kv8("op_attn_decode_kv8_mq", true, nh, nkv, max_seq,
+                            pos, window, nchunk, repeats, q, k8, v8, ks, vs,
+                            out, device);
 }
 
 // Host only: the KV-cache plan of engine create for this config and max_seq:
@@ -598,10 +620,10 @@ extern "C" int cake_hip_kv_dispatch(const char* config_json, int max_seq,
   out[0] = c.kv8 ? 1 : 0;
   out[1] = (int64_t)kv_layer_bytes(c, max_seq);
   out[2] = (int64_t)kv_scratch_bytes(c, max_seq);
-  out[3] = c.kv8 ? attn_decode_kv8_group(c.nh, c.nkv)
-           : c.attn_mq ? c.nh / c.nkv
-                       : cake_hip_attn_decode_group(c.nh, c.nkv, c.hd());
-  out[4] = c.kv8 ? attn_decode_kv8_grid_y(c.nh, c.nkv) : c.nh / out[3];
+  out[3] = c.attn_mq || c.attn_kv8_mq ? c.nh / c.nkv
+           : c.kv8 ? attn_decode_kv8_group(c.nh, c.nkv)
+                   : cake_hip_attn_decode_group(c.nh, c.nkv, c.hd());
+  out[4] = c.nh / out[3];
   return 0;
 }
 

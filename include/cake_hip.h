@@ -295,6 +295,14 @@ int cake_hip_op_attn_decode_kv8(int nh, int nkv, int max_seq, int pos,
                                 const float *q, const uint8_t *k8,
                                 const uint8_t *v8, const float *ks,
                                 const float *vs, float *out, int device);
+/* The same over k_attn_decode_kv8_mq, the grouped MFMA kernel over the codes
+ * (one block per chunk and kv head serves all nh / nkv <= 16 q-heads; the
+ * route of decode_attention "mfma_kv8").  More q-heads per kv head: error 5. */
+int cake_hip_op_attn_decode_kv8_mq(int nh, int nkv, int max_seq, int pos,
+                                   int window, int nchunk, int repeats,
+                                   const float *q, const uint8_t *k8,
+                                   const uint8_t *v8, const float *ks,
+                                   const float *vs, float *out, int device);
 /* Host only: the KV-cache plan of engine create.  The top-level config key
  * kv_cache_dtype selects the format: "bf16" (the default) or "fp8_e4m3"
  * (head_dim 128 only; anything else is error 5).  out = {format (0 bf16, 1
@@ -307,7 +315,10 @@ int cake_hip_op_attn_decode_kv8(int nh, int nkv, int max_seq, int pos,
  * serves all nh / nkv q-heads of a kv head from one K/V read (out[3] = nh /
  * nkv, out[4] = nkv).  "mfma" needs head_dim 64 or 128, nh / nkv <= 16 and the
  * bf16 cache; anything else, and any other value, is error 5 here and at
- * engine create, with decode_attention named in the message.  The environment
+ * engine create, with decode_attention named in the message.
+ * "mfma_kv8" is the same work split over the fp8 codes (k_attn_decode_kv8_mq;
+ * out[3] = nh / nkv, out[4] = nkv): it needs kv_cache_dtype "fp8_e4m3" and
+ * nh / nkv <= 16, and is refused in the same way otherwise.  The environment
  * variable CAKE_ATTN_MQ=1 (read per launch) routes eligible shapes there
  * without the key; cake_hip_attn_decode_path then answers 4. */
 int cake_hip_kv_dispatch(const char *config_json, int max_seq, int64_t out[5]);
