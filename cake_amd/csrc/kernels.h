@@ -183,9 +183,10 @@ int attn_decode_path(int nh, int nkv, int hd, int nchunk, int mq = -1);
 // attn_decode_mq_on: whether launch_attn_decode routes here for this mq
 // argument (-1 = CAKE_ATTN_MQ): hd 64 | 128, nh % nkv == 0, G <= 16.
 // ws as launch_attn_decode; cnt: nkv words, modulo-nchunk election, and the
-// elected block stores 0 to its word; nchunk == 1 uses neither.  The launcher
-// checks 1 <= nchunk <= 64 and the shape itself: outside them it launches
-// nothing and says so on stderr.
+// elected block stores 0 to its word; nchunk == 1 uses neither (the protocol is
+// mq_epilogue in attn_mq_common.h, shared with the fp8 kernel below).  The
+// launcher checks 1 <= nchunk <= 64 and the shape itself: outside them it
+// launches nothing and says so on stderr.
 bool attn_decode_mq_on(int nh, int nkv, int hd, int mq);
 void launch_attn_decode_mq(const u16* q, const u16* kc, const u16* vc,
                            const int* pos, float* ws, u32* cnt, u16* out,
@@ -218,9 +219,9 @@ void launch_attn_decode_kv8(const u16* q, const unsigned char* k8,
 // (kernels_kv8_mq.hip; config decode_attention "mfma_kv8"): grid (nchunk,
 // nkv), all G = nh / nkv q-heads of a kv head in one block, codes read and
 // converted once per kv head.  attn_decode_kv8_mq_on: nh % nkv == 0, G <= 16.
-// ws as launch_attn_decode; cnt: nkv words, modulo-nchunk election, the
-// elected block stores 0 to its word.  The launcher checks 1 <= nchunk <= 64
-// and the shape itself: outside them it launches nothing and says so on stderr.
+// ws / cnt exactly as launch_attn_decode_mq (the same mq_epilogue of
+// attn_mq_common.h).  The launcher checks 1 <= nchunk <= 64 and the shape
+// itself: outside them it launches nothing and says so on stderr.
 bool attn_decode_kv8_mq_on(int nh, int nkv);
 void launch_attn_decode_kv8_mq(const u16* q, const unsigned char* k8,
                                const unsigned char* v8, const float* ks,

@@ -175,12 +175,8 @@ __global__ __launch_bounds__(256) void k_attn_decode_fused(
   const int h = blockIdx.y;
   const int chunk = blockIdx.x;
   const int n = *pos + 1;
-  // sliding window (cache.rs:173-205 semantics): attention spans only the
-  // last `window` positions; chunks partition [lo, n)
-  const int lo = (window > 0 && n > window) ? n - window : 0;
-  const int cs = (n - lo + nchunk - 1) / nchunk;
-  const int start = lo + chunk * cs;
-  const int end = min(start + cs, n);
+  const DecodeSpan sp = decode_span(n, window, nchunk, chunk);
+  const int start = sp.start, end = sp.end;
   const int kvh = h / (nh / nkv);
   const int t = threadIdx.x, wid = t / WAVE, lane = t % WAVE;
   const int e0 = 2 * lane;             // dims (2*lane, 2*lane+1)
@@ -664,10 +660,8 @@ __global__ __launch_bounds__(256) void k_attn_decode_g(
   const int h0 = kvh * (nh / nkv) + sub * GB;
   const int chunk = blockIdx.x;
   const int n = *pos + 1;
-  const int lo = (window > 0 && n > window) ? n - window : 0;
-  const int cs = (n - lo + nchunk - 1) / nchunk;
-  const int start = lo + chunk * cs;
-  const int end = min(start + cs, n);
+  const DecodeSpan sp = decode_span(n, window, nchunk, chunk);
+  const int start = sp.start, end = sp.end;
   const int t = threadIdx.x, wid = t / WAVE, lane = t % WAVE;
   const float scale = rsqrtf(128.f);
   const u16* kbase = kc + (size_t)kvh * max_seq * hd;
@@ -1050,10 +1044,8 @@ __global__ __launch_bounds__(1024) void k_attn_decode_short(
   const int hs = wid / NCH;   // the head this wave serves
   const int chunk = wid % NCH;
   const int n = *pos + 1;
-  const int lo = (window > 0 && n > window) ? n - window : 0;
-  const int cs = (n - lo + NCH - 1) / NCH;
-  const int start = lo + chunk * cs;
-  const int end = min(start + cs, n);
+  const DecodeSpan sp = decode_span(n, window, NCH, chunk);
+  const int start = sp.start, end = sp.end;
   const float scale = rsqrtf(128.f);
   const u16* kbase = kc + (size_t)kvh * max_seq * hd;
   const u16* vbase = vc + (size_t)kvh * max_seq * hd;
@@ -1093,7 +1085,7 @@ __global__ __launch_bounds__(1024) void k_attn_decode_short(
 
   float m = -INFINITY, lsum = 0.f, o0 = 0.f, o1 = 0.f;
   const int nt = start < end ? (end - start + TILE - 1) / TILE : 0;
-  const int ntmax = (cs + TILE - 1) / TILE;  // chunk 0's count: block-uniform
+  const int ntmax = (sp.cs + TILE - 1) / TILE;  // chunk 0's: block-uniform
   for (int ti = 0; ti < ntmax; ++ti) {
     const int tb = start + ti * TILE;
     stage_write(rk);
@@ -1235,18 +1227,6 @@ int attn_decode_path(int nh, int nkv, int hd, int nchunk, int mq) {
 // free for the fragment reads.  Waves outside their causal/window tile
 // range skip compute but keep staging/waits/barriers uniform.
 // ---------------------------------------------------------------------------
-// lane<->lane+32 half exchange via v_permlane32_swap + cndmask (2-3 VALU)
-// instead of __shfl_xor(.,32) (ds_bpermute + lgkm wait on the LDS pipe)
-__device__ inline u32 halfswap32(u32 x, int lhalf) {
-  auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false);
-  return lhalf == 0 ? (u32)r[1] : (u32)r[0];
-}
-__device__ inline float halfswap32f(float x, int lhalf) {
-  union { float f; u32 u; } a{x};
-  a.u = halfswap32(a.u, lhalf);
-  return a.f;
-}
-
 // NW = waves per block (8 => 256 q rows/block, 4 => 128).  At S=2048 the
 // NW=8 grid is EXACTLY 256 blocks on 256 CUs with causally skewed work
 // (first q block 8 KV tiles, last 64): one block per CU means the chip

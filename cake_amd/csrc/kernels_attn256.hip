@@ -77,10 +77,8 @@ __global__ __launch_bounds__(256) void k_attn_decode_256(
   const int h0 = kvh * (nh / nkv) + sub * GB;
   const int chunk = blockIdx.x;
   const int n = *pos + 1;
-  const int lo = (window > 0 && n > window) ? n - window : 0;
-  const int cs = (n - lo + nchunk - 1) / nchunk;
-  const int start = lo + chunk * cs;
-  const int end = min(start + cs, n);
+  const DecodeSpan sp = decode_span(n, window, nchunk, chunk);
+  const int start = sp.start, end = sp.end;
   const int t = threadIdx.x, wid = t / WAVE, lane = t % WAVE;
   const int dgrp = t & 31, prow = t >> 5;
   const float scale = rsqrtf((float)HD);

@@ -100,7 +100,10 @@ namespace {
     __attribute__((target("no-packed-fp32-ops"))), apply_to = function)
 #endif
 
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
+// halfswap32f and pack_bf16 are this file's own copies of the helpers of the
+// same names in kernels_common.h: those are compiled with the packed-f32 forms
+// enabled, a different target-feature set from the functions in this region,
+// and might no longer inline into the kernel.
 
 // x of lane ^ 32
 __device__ inline float halfswap32f(float x, int lhalf) {

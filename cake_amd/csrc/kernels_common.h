@@ -18,6 +18,7 @@ using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 using short8 = __attribute__((ext_vector_type(8))) short;
 using uint4v = __attribute__((ext_vector_type(4))) unsigned int;
 using f32x2 = __attribute__((ext_vector_type(2))) float;
+using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
 
 // bf16 <-> f32 (round-to-nearest-even, matches torch/HF casting)
 __device__ __host__ inline u16 f2b(float f) {
@@ -68,6 +69,43 @@ __device__ inline float gumbel_noise(uint64_t base, int i) {
   const u32 k = min((u32)(z >> 40), 0xfffffeu);
   const float u = (float)(k + 1u) * 0x1p-24f;
   return -__logf(-__logf(u));
+}
+
+// lane<->lane+32 half exchange via v_permlane32_swap + cndmask (2-3 VALU)
+// instead of __shfl_xor(.,32) (ds_bpermute + lgkm wait on the LDS pipe)
+__device__ inline u32 halfswap32(u32 x, int lhalf) {
+  auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false);
+  return lhalf == 0 ? (u32)r[1] : (u32)r[0];
+}
+__device__ inline float halfswap32f(float x, int lhalf) {
+  union { float f; u32 u; } a{x};
+  a.u = halfswap32(a.u, lhalf);
+  return a.f;
+}
+// two f32 -> packed bf16 pair, round to nearest even (v_cvt_pk_bf16_f32)
+__device__ inline u32 pack_bf16(float lo, float hi) {
+  f32x2 v = {lo, hi};
+  union { bf16x2 b; u32 u; } c{__builtin_convertvector(v, bf16x2)};
+  return c.u;
+}
+
+// Split-KV chunk partition of decode attention at n = *pos + 1 live positions.
+// Sliding window (cache.rs:173-205 semantics): attention spans only the last
+// `window` positions; the nchunk chunks partition [lo, n), chunk `chunk` is
+// [start, end) (empty when start >= end); cs is the unclipped chunk length,
+// which is chunk 0's.  Every kernel that is handed the same ws / cnt must cut
+// the span the same way: this is the one definition.  Forced inline because
+// kernels_kv8.hip compiles its functions for another target-feature set
+// (no-packed-fp32-ops), into which a plain inline function of this header
+// stays a call.
+struct DecodeSpan { int start, end, cs; };
+__host__ __device__ __forceinline__ DecodeSpan decode_span(int n, int window,
+                                                           int nchunk,
+                                                           int chunk) {
+  const int lo = (window > 0 && n > window) ? n - window : 0;
+  const int cs = (n - lo + nchunk - 1) / nchunk;
+  const int start = lo + chunk * cs;
+  return {start, min(start + cs, n), cs};
 }
 
 __device__ inline float wave_sum(float v) {
