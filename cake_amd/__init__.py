@@ -460,7 +460,9 @@ def attn_decode_path(nh, nkv, hd, nchunk):
     default at nchunk 4).  The library reads CAKE_ATTN_SHORT on every call:
     0 = never the short kernel, 2 = also at nchunk 8.  hd 256: 3.  With
     CAKE_ATTN_MQ=1 (read on every call) hd 64 | 128 with at most 16 q-heads
-    per kv head: 4, the grouped MFMA kernel."""
+    per kv head: 4, the grouped MFMA kernel.  With CAKE_ATTN_MQ256=1 (read on
+    every call) hd 256 with at most 16 q-heads per kv head: 5, its hd-256
+    form; CAKE_ATTN_MQ has no effect at hd 256."""
     return _lib.cake_hip_attn_decode_path(nh, nkv, hd, nchunk)
 
 
@@ -469,7 +471,8 @@ def attn_decode_group(nh, nkv, hd):
     (host only).  hd 256: the largest of 4, 3, 2, 1 dividing nh / nkv, capped
     by CAKE_ATTN256_GB, which the library reads on every call (default 1: the
     per-head route measured faster; 2..4 opt in to grouping).  Under
-    CAKE_ATTN_MQ=1 (decode path 4): nh / nkv."""
+    CAKE_ATTN_MQ=1 (decode path 4), and at hd 256 under CAKE_ATTN_MQ256=1
+    (decode path 5): nh / nkv."""
     return _lib.cake_hip_attn_decode_group(nh, nkv, hd)
 
 
@@ -1053,7 +1056,8 @@ class Engine:
         what the config says (decode_attention, default "auto"); "auto" |
         "mfma" (the grouped MFMA decode kernel: head_dim 64 | 128, at most 16
         q-heads per kv head, bf16 cache) | "mfma_kv8" (the same over an
-        fp8_e4m3 cache) overrides it."""
+        fp8_e4m3 cache) | "mfma_256" (the same at head_dim 256, bf16 cache)
+        overrides it."""
         if isinstance(config, dict):
             config = json.dumps(config)
         if kv_dtype is not None:

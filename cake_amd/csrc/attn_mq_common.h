@@ -1,6 +1,9 @@
 // What the grouped MFMA decode kernels share: k_attn_decode_mq<64|128>
 // (kernels_attn_mq.hip, bf16 cache) and k_attn_decode_kv8_mq
-// (kernels_kv8_mq.hip, e4m3 cache).  Included by those two files only.
+// (kernels_kv8_mq.hip, e4m3 cache).  Included by those two files and by
+// kernels_attn_mq256.hip, whose k_attn_decode_mq256 keeps this contract with a
+// 16-position wave step (wave w owns start + 16 w + 64 i .. + 16) and a softmax
+// step of its own, and ends in the same mq_epilogue.
 //
 // Work split.  Grid (nchunk, nkv), 4 waves.  A block serves all G <= 16 heads
 // of kv head blockIdx.y, padded to ONE 16-row MFMA operand, over chunk

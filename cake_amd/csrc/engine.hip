@@ -371,12 +371,14 @@ int parse_config(const char* json, ModelConfig* c) {
   if (auto p = root->get("decode_attention"))
     if (!p->is_null()) {
       if (p->kind != minijson::Value::Str ||
-          (p->str != "auto" && p->str != "mfma" && p->str != "mfma_kv8"))
+          (p->str != "auto" && p->str != "mfma" && p->str != "mfma_kv8" &&
+           p->str != "mfma_256"))
         return set_err(5, "config.json: decode_attention %s is not supported "
-                          "(auto, mfma or mfma_kv8)",
+                          "(auto, mfma, mfma_kv8 or mfma_256)",
                        p->kind == minijson::Value::Str ? p->str.c_str() : "?");
       c->attn_mq = p->str == "mfma";
       c->attn_kv8_mq = p->str == "mfma_kv8";
+      c->attn_mq256 = p->str == "mfma_256";
     }
   if (c->fused_ckpt && c->fp8)
     return set_err(5, "config.json: quant_method fp8 with model_type phi3 is "
@@ -500,9 +502,20 @@ int kv8_config_err(const ModelConfig& c) {
                       "128 (got head_dim %d)", c.hd());
   return 0;
 }
-// decode_attention "mfma" and "mfma_kv8" (host only; engine create and
-// cake_hip_kv_dispatch)
+// decode_attention "mfma", "mfma_kv8" and "mfma_256" (host only; engine create
+// and cake_hip_kv_dispatch)
 int attn_mq_config_err(const ModelConfig& c) {
+  if (c.attn_mq256) {
+    if (c.kv8)
+      return set_err(5, "config.json: decode_attention mfma_256 reads the "
+                        "bf16 KV cache (got kv_cache_dtype fp8_e4m3)");
+    if (c.hd() != 256 || !attn_decode_mq256_on(c.nh, c.nkv, 1))
+      return set_err(5, "config.json: decode_attention mfma_256 needs "
+                        "head_dim 256 and at most 16 q-heads per kv head (got "
+                        "head_dim %d, %d q-heads, %d kv heads)", c.hd(), c.nh,
+                     c.nkv);
+    return 0;
+  }
   if (c.attn_kv8_mq) {
     if (!c.kv8)
       return set_err(5, "config.json: decode_attention mfma_kv8 reads the "
@@ -915,7 +928,7 @@ static void enqueue_layer_decode(cake_engine* e, LayerDev& l,
     launch_attn_decode(e->qkv, l.kc, l.vc, e->dev_pos, e->attn_ws,
                        e->attn_cnt, e->attn_out, c.nh, c.nkv, hd, e->max_seq,
                        e->nchunk, c.win_for(l.idx), e->stream,
-                       c.attn_mq ? 1 : -1);
+                       c.attn_mq ? 1 : -1, c.attn_mq256 ? 1 : -1);
   }
   if (c.gemma3) {  // sandwich norms: o and down go through their post-norm
     enqueue_post_proj(e, l.o, "gemv_o", e->attn_out, l.post1);
@@ -1608,10 +1621,15 @@ extern "C" int cake_hip_decode(cake_engine* e, int steps,
   // the grouped MFMA kernel (decode_attention "mfma" or CAKE_ATTN_MQ) has
   // nkv blocks per chunk and follows the grouped curve; an fp8 KV cache
   // never runs it, whatever the environment says: there only
-  // decode_attention "mfma_kv8" selects the grouped MFMA kernel over the codes
-  const bool mq = e->c.kv8 ? e->c.attn_kv8_mq
-                           : attn_decode_mq_on(e->c.nh, e->c.nkv, e->c.hd(),
-                                               e->c.attn_mq ? 1 : -1);
+  // decode_attention "mfma_kv8" selects the grouped MFMA kernel over the codes.
+  // The hd-256 form (decode_attention "mfma_256" or CAKE_ATTN_MQ256) has nkv
+  // blocks per chunk too and takes the same curve, not retuned for it.
+  const bool mq =
+      e->c.kv8 ? e->c.attn_kv8_mq
+      : e->c.hd() == 256
+          ? attn_decode_mq256_on(e->c.nh, e->c.nkv, e->c.attn_mq256 ? 1 : -1)
+          : attn_decode_mq_on(e->c.nh, e->c.nkv, e->c.hd(),
+                              e->c.attn_mq ? 1 : -1);
   const int gy =
       mq ? e->c.nkv : attn_decode_grid_y(e->c.nh, e->c.nkv, e->c.hd());
   auto want_nchunk = [gy](int pos) {

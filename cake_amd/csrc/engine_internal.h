@@ -91,6 +91,11 @@ struct ModelConfig {
   // grouped MFMA kernel over the codes (kernels_kv8_mq.hip).  fp8_e4m3 cache
   // (hence hd 128), G <= 16 (attn_mq_config_err).
   bool attn_kv8_mq = false;
+  // decode_attention "mfma_256": decode attention at head dim 256 runs the
+  // grouped MFMA kernel k_attn_decode_mq256 (kernels_attn_mq256.hip;
+  // launch_attn_decode's mq256 = 1).  hd 256, G <= 16, bf16 cache
+  // (attn_mq_config_err).
+  bool attn_mq256 = false;
   // llama3 rope scaling (config.rs:50-65)
   bool rope_llama3 = false;
   float rs_factor = 1, rs_low = 1, rs_high = 4;
@@ -126,7 +131,8 @@ int mx4_config_err(const ModelConfig& c);
 // fp8 KV cache: head_dim 128 only
 int kv8_config_err(const ModelConfig& c);
 // decode_attention "mfma": head_dim 64 | 128, nh / nkv <= 16, bf16 KV cache;
-// "mfma_kv8": fp8_e4m3 KV cache, nh / nkv <= 16
+// "mfma_kv8": fp8_e4m3 KV cache, nh / nkv <= 16; "mfma_256": head_dim 256,
+// nh / nkv <= 16, bf16 KV cache
 int attn_mq_config_err(const ModelConfig& c);
 // bytes of one layer's KV cache in the config's format, and of the engine-wide
 // bf16 scratch an fp8 cache attends through in prefill (0 for bf16)

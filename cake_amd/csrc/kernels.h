@@ -163,11 +163,13 @@ void launch_rope_store_prefill(u16* qkv, u16* kc, u16* vc, u16* vtc,
                                const u16* kn, float eps, hipStream_t s,
                                const float* bias = nullptr);
 // mq: 1 = run the grouped MFMA kernel (kernels_attn_mq.hip) when the shape is
-// eligible, 0 = never, -1 = read CAKE_ATTN_MQ per launch (unset = 0)
+// eligible, 0 = never, -1 = read CAKE_ATTN_MQ per launch (unset = 0).
+// mq256: the same for the hd-256 grouped MFMA kernel (kernels_attn_mq256.hip)
+// and CAKE_ATTN_MQ256; mq has no effect at hd 256 and mq256 none elsewhere.
 void launch_attn_decode(const u16* q, const u16* kc, const u16* vc,
                         const int* pos, float* ws, u32* cnt, u16* out, int nh,
                         int nkv, int hd, int max_seq, int nchunk, int window,
-                        hipStream_t s, int mq = -1);
+                        hipStream_t s, int mq = -1, int mq256 = -1);
 // grid_y of the GQA-grouped decode-attention kernel for this head geometry
 // (0 = per-head fallback kernel); the engine's chunk-count policy uses it.
 // hd 256: nh / attn256_group(nh, nkv), never 0.
@@ -175,8 +177,10 @@ int attn_decode_grid_y(int nh, int nkv, int hd);
 // which kernel launch_attn_decode runs for (geometry, nchunk): 0 per-head,
 // 1 grouped, 2 short-context in-block split-KV (CAKE_ATTN_SHORT=0 -> 1),
 // 3 the hd-256 kernel (kernels_attn256.hip), 4 the grouped MFMA kernel
-// (kernels_attn_mq.hip; only when mq / CAKE_ATTN_MQ asks for it)
-int attn_decode_path(int nh, int nkv, int hd, int nchunk, int mq = -1);
+// (kernels_attn_mq.hip; only when mq / CAKE_ATTN_MQ asks for it), 5 its
+// hd-256 form (kernels_attn_mq256.hip; only under mq256 / CAKE_ATTN_MQ256)
+int attn_decode_path(int nh, int nkv, int hd, int nchunk, int mq = -1,
+                     int mq256 = -1);
 // Grouped MFMA decode attention, k_attn_decode_mq<64 | 128>
 // (kernels_attn_mq.hip): grid (nchunk, nkv), one block serves all G = nh / nkv
 // q-heads of a kv head as one 16-row MFMA operand, K/V read once per kv head.
@@ -192,6 +196,17 @@ void launch_attn_decode_mq(const u16* q, const u16* kc, const u16* vc,
                            const int* pos, float* ws, u32* cnt, u16* out,
                            int nh, int nkv, int hd, int max_seq, int nchunk,
                            int window, hipStream_t s);
+// Grouped MFMA decode attention at hd 256, k_attn_decode_mq256
+// (kernels_attn_mq256.hip): the same grid, ws / cnt protocol and launcher
+// checks as launch_attn_decode_mq, with a 16-position wave step.
+// attn_decode_mq256_on: whether launch_attn_decode routes an hd-256 shape here
+// for this mq256 argument (-1 = CAKE_ATTN_MQ256 per call, unset = 0):
+// nh % nkv == 0, G <= 16.  The caller checks the head dim.
+bool attn_decode_mq256_on(int nh, int nkv, int mq256);
+void launch_attn_decode_mq256(const u16* q, const u16* kc, const u16* vc,
+                              const int* pos, float* ws, u32* cnt, u16* out,
+                              int nh, int nkv, int max_seq, int nchunk,
+                              int window, hipStream_t s);
 // fp8 (e4m3) KV cache, hd 128 (kernels_kv8.hip).  k8 / v8: u8 (nkv, max_seq,
 // 128) codes; ks / vs: f32 (nkv, max_seq) power-of-two row scales; kc / vc /
 // vtc: the bf16 scratch of one layer's size.

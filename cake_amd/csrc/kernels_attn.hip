@@ -1201,10 +1201,11 @@ int attn_decode_grid_y(int nh, int nkv, int hd) {
 // end (profiles/short_attn_NOTES.md), so there it runs only under
 // CAKE_ATTN_SHORT=2.  CAKE_ATTN_SHORT=0 restores the grouped routing
 // everywhere.  The knob is read per launch so a test can flip it.
-// 4 = the grouped MFMA kernel (kernels_attn_mq.hip), opt-in through mq.
-int attn_decode_path(int nh, int nkv, int hd, int nchunk, int mq) {
+// 4 = the grouped MFMA kernel (kernels_attn_mq.hip), opt-in through mq;
+// 5 = its hd-256 form (kernels_attn_mq256.hip), opt-in through mq256.
+int attn_decode_path(int nh, int nkv, int hd, int nchunk, int mq, int mq256) {
   if (attn_decode_mq_on(nh, nkv, hd, mq)) return 4;
-  if (hd == 256) return 3;
+  if (hd == 256) return attn_decode_mq256_on(nh, nkv, mq256) ? 5 : 3;
   if (attn_decode_grid_y(nh, nkv, hd) <= 0) return 0;
   const char* e = getenv("CAKE_ATTN_SHORT");
   const int mode = e ? atoi(e) : 1;
@@ -1700,10 +1701,15 @@ void launch_rope_store_prefill(u16* qkv, u16* kc, u16* vc, u16* vtc,
 void launch_attn_decode(const u16* q, const u16* kc, const u16* vc,
                         const int* pos, float* ws, u32* cnt, u16* out, int nh,
                         int nkv, int hd, int max_seq, int nchunk, int window,
-                        hipStream_t s, int mq) {
+                        hipStream_t s, int mq, int mq256) {
   if (attn_decode_mq_on(nh, nkv, hd, mq)) {
     launch_attn_decode_mq(q, kc, vc, pos, ws, cnt, out, nh, nkv, hd, max_seq,
                           nchunk, window, s);
+    return;
+  }
+  if (hd == 256 && attn_decode_mq256_on(nh, nkv, mq256)) {
+    launch_attn_decode_mq256(q, kc, vc, pos, ws, cnt, out, nh, nkv, max_seq,
+                             nchunk, window, s);
     return;
   }
   if (hd == 256) {
@@ -1712,7 +1718,7 @@ void launch_attn_decode(const u16* q, const u16* kc, const u16* vc,
     return;
   }
   const int gy = attn_decode_grid_y(nh, nkv, hd);
-  if (attn_decode_path(nh, nkv, hd, nchunk, 0) == 2) {
+  if (attn_decode_path(nh, nkv, hd, nchunk, 0, 0) == 2) {
     // tile image per chunk + scores[16][64] + q f32 [HPB][128] + partial
     // o [16][128] + m/l [16] each
     const size_t smem = (size_t)nchunk * 64 * 256 + 16 * 64 * 4 +

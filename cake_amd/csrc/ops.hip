@@ -393,10 +393,12 @@ extern "C" int cake_hip_attn_decode_path(int nh, int nkv, int hd, int nchunk) {
 // q-heads per block of the decode-attention kernel at this geometry (host
 // only): hd 256 -> attn256_group under CAKE_ATTN256_GB; hd 128 -> the grouped
 // kernel's 4|2|1; anything else, or a per-head route, 1.  Under CAKE_ATTN_MQ
-// the grouped MFMA kernel serves all nh / nkv heads of a kv head.
+// the grouped MFMA kernel serves all nh / nkv heads of a kv head, and under
+// CAKE_ATTN_MQ256 its hd-256 form does.
 extern "C" int cake_hip_attn_decode_group(int nh, int nkv, int hd) {
   if (nh <= 0 || nkv <= 0 || nh % nkv != 0) return 1;
   if (attn_decode_mq_on(nh, nkv, hd, -1)) return nh / nkv;
+  if (hd == 256 && attn_decode_mq256_on(nh, nkv, -1)) return nh / nkv;
   if (hd == 256) return attn256_group(nh, nkv);
   const int gy = attn_decode_grid_y(nh, nkv, hd);
   return gy > 0 ? nh / gy : 1;
@@ -620,7 +622,7 @@ extern "C" int cake_hip_kv_dispatch(const char* config_json, int max_seq,
   out[0] = c.kv8 ? 1 : 0;
   out[1] = (int64_t)kv_layer_bytes(c, max_seq);
   out[2] = (int64_t)kv_scratch_bytes(c, max_seq);
-  out[3] = c.attn_mq || c.attn_kv8_mq ? c.nh / c.nkv
+  out[3] = c.attn_mq || c.attn_kv8_mq || c.attn_mq256 ? c.nh / c.nkv
            : c.kv8 ? attn_decode_kv8_group(c.nh, c.nkv)
                    : cake_hip_attn_decode_group(c.nh, c.nkv, c.hd());
   out[4] = c.nh / out[3];

@@ -300,11 +300,12 @@ def main():
                     help="KV-cache format; fp8_e4m3 (head_dim 128 models) "
                     "stores e4m3 codes with a power-of-two scale per row")
     ap.add_argument("--decode-attention", default=None,
-                    choices=("auto", "mfma", "mfma_kv8"),
+                    choices=("auto", "mfma", "mfma_kv8", "mfma_256"),
                     help="decode-attention kernel; mfma (head_dim 64 | 128, at "
                     "most 16 q-heads per kv head, bf16 cache) reads K/V once "
                     "per kv head through the grouped MFMA kernel; mfma_kv8 is "
-                    "the same over an fp8_e4m3 KV cache")
+                    "the same over an fp8_e4m3 KV cache, mfma_256 the same "
+                    "at head_dim 256 (bf16 cache)")
     args = ap.parse_args()
 
     import cake_amd

@@ -251,12 +251,15 @@ int cake_hip_attn_dispatch(int S, int nh, int nkv, int hd, int out[6]);
  * geometry and chunk count: 0 = per-head, 1 = grouped, 2 = short-context
  * (all chunks of a head in one workgroup; nchunk 4), 3 = the hd-256 kernel.
  * CAKE_ATTN_SHORT, read on every call: 0 = never the short kernel, 2 = also
- * at nchunk 8. */
+ * at nchunk 8.  4 = the grouped MFMA kernel (CAKE_ATTN_MQ=1, hd 64 | 128),
+ * 5 = its hd-256 form k_attn_decode_mq256 (CAKE_ATTN_MQ256=1, read on every
+ * call; nh / nkv <= 16).  CAKE_ATTN_MQ has no effect at hd 256. */
 int cake_hip_attn_decode_path(int nh, int nkv, int hd, int nchunk);
 /* Host only: q-heads served by one block of the decode-attention kernel at
  * this geometry.  hd 256: the largest of 4, 3, 2, 1 that divides nh / nkv,
  * capped by CAKE_ATTN256_GB (read on every call).  The cap defaults to 1 (per
- * head), which measured faster; 2..4 opt in to the grouped kernel. */
+ * head), which measured faster; 2..4 opt in to the grouped kernel.  Under
+ * CAKE_ATTN_MQ256=1 (decode path 5): nh / nkv. */
 int cake_hip_attn_decode_group(int nh, int nkv, int hd);
 /* cake_hip_op_attn_decode with a chunk count PER LAUNCH: nlaunch (1..16)
  * launches back to back on one set of buffers, launch i split over
@@ -318,9 +321,14 @@ int cake_hip_op_attn_decode_kv8_mq(int nh, int nkv, int max_seq, int pos,
  * engine create, with decode_attention named in the message.
  * "mfma_kv8" is the same work split over the fp8 codes (k_attn_decode_kv8_mq;
  * out[3] = nh / nkv, out[4] = nkv): it needs kv_cache_dtype "fp8_e4m3" and
- * nh / nkv <= 16, and is refused in the same way otherwise.  The environment
- * variable CAKE_ATTN_MQ=1 (read per launch) routes eligible shapes there
- * without the key; cake_hip_attn_decode_path then answers 4. */
+ * nh / nkv <= 16, and is refused in the same way otherwise.
+ * "mfma_256" is the grouped MFMA kernel for head_dim 256 (k_attn_decode_mq256,
+ * a 16-position wave step; out[3] = nh / nkv, out[4] = nkv): it needs head_dim
+ * 256, nh / nkv <= 16 and the bf16 cache, and is refused in the same way
+ * otherwise.  The environment variable CAKE_ATTN_MQ=1 (read per launch) routes
+ * eligible hd 64 | 128 shapes to the "mfma" kernel without the key
+ * (cake_hip_attn_decode_path then answers 4), CAKE_ATTN_MQ256=1 eligible hd-256
+ * shapes to the "mfma_256" kernel (path 5). */
 int cake_hip_kv_dispatch(const char *config_json, int max_seq, int64_t out[5]);
 
 /* Linear-layer op entries (test-only): GEMV, fp8 GEMV, gate-up, fused
